@@ -9,7 +9,9 @@ head -> decode + class-aware NMS + top-k + rescale -> List[Dict], with the image
 every rank runs its own shard (weak scaling: `batch` images per GPU) and the fixed-shape detection slabs are all-gathered
 over RCCL.
 
-Rank 0 prints ONE JSON line: BASELINE.json's metric plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly --steps steps once and prints BASELINE.json's metric
+(`value`, `ms_per_step`, the workload in `config`); `--dump-outputs DIR` writes the detections of the last timed step as .npy files.
+`--full` repeats the timed region (--repeats / --min-seconds) and adds every secondary measurement and check:
   "roofline"     : the conv stack (dominant kernel family: conv_igemm_v2_kernel / conv3x3_halo_kernel / conv_halo8_kernel /
                    conv_stem_planar_kernel / conv_head_decode_group_kernel) -- algorithmic bytes per launch / average launch
                    time, where the launch time comes from HIP events recorded on the plan's own stream around the conv
@@ -75,9 +77,14 @@ def parse():
     ap.add_argument("--head-gain", type=float, default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default: min(host cpus, 32))")
-    ap.add_argument("--per-op", default="", help="write a per-op profile (json) to this path after the timed run")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region of --steps steps is run this many times back to back; value / ms_per_step are the MEDIAN repeat, all repeats are reported")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="keep repeating the timed region until the regions add up to this much wall time (>= --repeats regions)")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements and checks (roofline event brackets, serial / serving / dynamic-shape "
+                                                            "throughput, parity, CPU baseline, --per-op) and repeat the timed region; off: the headline line alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the detections of the last timed step (rank 0) to DIR/<name>.npy as float32")
+    ap.add_argument("--per-op", default="", help="write a per-op profile (json) to this path after the timed run (needs --full)")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region of --steps steps is run this many times back to back; value / ms_per_step are the MEDIAN repeat, "
+                                                                "all repeats are reported (default: 5 with --full, else 1)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="keep repeating the timed region until the regions add up to this much wall time (>= --repeats regions; "
+                                                                    "default: 2.0 with --full, else 0)")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("YOLORT_AMD_GRAPH", "1")), help="replay the conv stack as a captured hipGraph (the package default since round 5; 0: per-kernel launches)")
     a = ap.parse_args()
     preset = CONFIGS[a.config]
@@ -89,7 +96,30 @@ def parse():
         a.steps = 20 if big else 60
     if a.warmup is None:
         a.warmup = 5 if big else 10
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    if a.min_seconds is None:
+        a.min_seconds = 2.0 if a.full else 0.0
+    if a.per_op and not a.full:
+        ap.error("--per-op needs --full")
     return a
+
+
+def dump_outputs(path, dets, k=300):
+    """what the timed path returned for its last step, as fixed-shape float32 arrays: boxes (B, k, 4), scores (B, k), labels (B, k), zero past each
+    image's count, and counts (B,)"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n = len(dets)
+    arrs = {"boxes": np.zeros((n, k, 4), np.float32), "scores": np.zeros((n, k), np.float32), "labels": np.zeros((n, k), np.float32), "counts": np.zeros((n,), np.float32)}
+    for i, d in enumerate(dets):
+        m = len(d["scores"])
+        arrs["counts"][i] = m
+        for name in ("boxes", "scores", "labels"):
+            arrs[name][i, :m] = d[name].float().cpu().numpy()
+    for name, a in arrs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -549,36 +579,15 @@ def main_fp32(args):
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     elapsed, host_enqueue_ms, dets = reps[order[len(order) // 2]]
     rep_ips = [round(args.batch * args.steps / r[0], 1) for r in reps]
-    # the conv launches with ONE batch in flight: HIP events on the stream they are launched on
-    yolo.bracket = {"pre": ([], []), "conv": ([], []), "post": ([], [])}
-    n_excl = 6
-    for _ in range(n_excl):
-        model.forward_async(images_gpu).result()
-        torch.cuda.synchronize()
-    excl = {k: _elapsed(v) for k, v in yolo.bracket.items()}
-    yolo.bracket = None
-    mean = lambda v: (sum(v) / len(v)) if v else 0.0  # noqa: E731
-    conv_meta = [m for m in e.plan.meta if m["kind"] == "conv"]
-    n_conv = len(conv_meta)
-    bytes_step, flops_step = sum(m["bytes"] for m in conv_meta), sum(m["flops"] for m in conv_meta)
-    bound_s = sum(max(m["flops"] / F32_MFMA_PEAK, m["bytes"] / HBM_PEAK) for m in conv_meta)
-    n_mfma_bound = sum(1 for m in conv_meta if m["flops"] / F32_MFMA_PEAK >= m["bytes"] / HBM_PEAK)
-    conv_s = mean(excl["conv"]) * 1e-3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, reps[-1][2])
     step_s = elapsed / args.steps
     ips = args.batch * args.steps / elapsed
+    conv_meta = [m for m in e.plan.meta if m["kind"] == "conv"]
+    n_conv = len(conv_meta)
     tiles = {}
     for m in conv_meta:
         tiles[str(m.get("tile"))] = tiles.get(str(m.get("tile")), 0) + 1
-    # HBM traffic of the fp32 conv launches from the committed PMC passes (rocprofv3 cannot run inside this process): per launch like `achieved`; only for the workload it was measured on
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "conv_traffic_fp32.json")
-    if os.path.exists(tpath) and args.config == "c2" and args.arch == CONFIGS["c2"]["arch"] and args.batch == 32 and args.size == 640:
-        with open(tpath) as f:
-            tj = json.load(f)
-        if "fetch_mb_per_step_corrected" in tj:
-            tb = (tj["fetch_mb_per_step_corrected"] + tj["write_mb_per_step"]) * 1e6
-            traffic = {"bytes_per_launch": round(tb / max(n_conv, 1)), "bytes_per_step": round(tb), "vs_algorithmic": round(tb / max(bytes_step, 1), 3),
-                       "source": "profiles/conv_traffic_fp32.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, tools/profile_serial.py --config c2 --fp32)", "correction": tj.get("correction")}
     out = {
         "metric": ("images/sec at 640x640 (bs=32) yolov5s" if args.config == "c2" else f"images/sec at {args.size}x{args.size} (bs={args.batch}) {args.arch}") + " -- fp32 mode",
         "value": round(ips, 2), "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_s * 1e3, 4),
@@ -591,19 +600,45 @@ def main_fp32(args):
                    "weights": f"seeded synthetic (workloads/synth.py, head_gain {args.head_gain})", "batches_in_flight": depth, "plan_instances": yolo.pipeline_depth,
                    "host_enqueue_ms_per_step_rank0": round(host_enqueue_ms, 4), "canvas": [e.x.h, e.x.w], "detections_per_step_rank0": int(sum(len(d["scores"]) for d in dets)),
                    "conv_tiles": tiles, "plan_activation_bytes": e.plan.bytes_allocated},
-        "roofline": {"bound": "mfma", "achieved": round(flops_step / conv_s / 1e12, 2) if conv_s > 0 else 0.0, "peak": F32_MFMA_PEAK / 1e12, "unit": "TFLOP/s",
-                     "frac": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0,
-                     "frac_definition": f"per-launch bound sum_l max(flops_l / 157.3 TFLOP/s, bytes_l / 8 TB/s) at 4 bytes per element / measured serial conv time; {n_mfma_bound} of {n_conv} launches are MFMA-bound",
-                     "frac_mfma": round(flops_step / conv_s / F32_MFMA_PEAK, 4) if conv_s > 0 else 0.0, "traffic": traffic,
-                     "kernel": "conv_f32_pipe_kernel (every conv launch of one step; csrc/conv_f32_pipe.hip)", "launches_per_step": n_conv,
-                     "algorithmic_flops_per_step": flops_step, "algorithmic_bytes_per_step": bytes_step, "algorithmic_flops_per_launch": round(flops_step / max(n_conv, 1)),
-                     "per_layer_bound_ms": round(bound_s * 1e3, 4),
-                     "serial": {"conv_ms_per_step": round(conv_s * 1e3, 4), "avg_launch_us": round(conv_s / max(n_conv, 1) * 1e6, 2),
-                                "timing": f"HIP events on the plan's stream around the conv launches, one batch in flight, mean of {n_excl} steps right after the timed region"},
-                     "pipelined": {"batches_in_flight": depth, "ms_per_step": round(step_s * 1e3, 4), "frac_of_per_layer_bound": round(bound_s / step_s, 4),
-                                   "tflops": round(flops_step / step_s / 1e12, 2)},
-                     "other_kernels": {"letterbox": {"ms": round(mean(excl["pre"]), 4)} if excl["pre"] else None, "postprocess": {"ms": round(mean(excl["post"]), 4)} if excl["post"] else None}},
     }
+    if not args.full:
+        print(json.dumps(out))
+        return
+    # the conv launches with ONE batch in flight: HIP events on the stream they are launched on
+    yolo.bracket = {"pre": ([], []), "conv": ([], []), "post": ([], [])}
+    n_excl = 6
+    for _ in range(n_excl):
+        model.forward_async(images_gpu).result()
+        torch.cuda.synchronize()
+    excl = {k: _elapsed(v) for k, v in yolo.bracket.items()}
+    yolo.bracket = None
+    mean = lambda v: (sum(v) / len(v)) if v else 0.0  # noqa: E731
+    bytes_step, flops_step = sum(m["bytes"] for m in conv_meta), sum(m["flops"] for m in conv_meta)
+    bound_s = sum(max(m["flops"] / F32_MFMA_PEAK, m["bytes"] / HBM_PEAK) for m in conv_meta)
+    n_mfma_bound = sum(1 for m in conv_meta if m["flops"] / F32_MFMA_PEAK >= m["bytes"] / HBM_PEAK)
+    conv_s = mean(excl["conv"]) * 1e-3
+    # HBM traffic of the fp32 conv launches from the committed PMC passes (rocprofv3 cannot run inside this process): per launch like `achieved`; only for the workload it was measured on
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "conv_traffic_fp32.json")
+    if os.path.exists(tpath) and args.config == "c2" and args.arch == CONFIGS["c2"]["arch"] and args.batch == 32 and args.size == 640:
+        with open(tpath) as f:
+            tj = json.load(f)
+        if "fetch_mb_per_step_corrected" in tj:
+            tb = (tj["fetch_mb_per_step_corrected"] + tj["write_mb_per_step"]) * 1e6
+            traffic = {"bytes_per_launch": round(tb / max(n_conv, 1)), "bytes_per_step": round(tb), "vs_algorithmic": round(tb / max(bytes_step, 1), 3),
+                       "source": "profiles/conv_traffic_fp32.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, tools/profile_serial.py --config c2 --fp32)", "correction": tj.get("correction")}
+    out["roofline"] = {"bound": "mfma", "achieved": round(flops_step / conv_s / 1e12, 2) if conv_s > 0 else 0.0, "peak": F32_MFMA_PEAK / 1e12, "unit": "TFLOP/s",
+                       "frac": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0,
+                       "frac_definition": f"per-launch bound sum_l max(flops_l / 157.3 TFLOP/s, bytes_l / 8 TB/s) at 4 bytes per element / measured serial conv time; {n_mfma_bound} of {n_conv} launches are MFMA-bound",
+                       "frac_mfma": round(flops_step / conv_s / F32_MFMA_PEAK, 4) if conv_s > 0 else 0.0, "traffic": traffic,
+                       "kernel": "conv_f32_pipe_kernel (every conv launch of one step; csrc/conv_f32_pipe.hip)", "launches_per_step": n_conv,
+                       "algorithmic_flops_per_step": flops_step, "algorithmic_bytes_per_step": bytes_step, "algorithmic_flops_per_launch": round(flops_step / max(n_conv, 1)),
+                       "per_layer_bound_ms": round(bound_s * 1e3, 4),
+                       "serial": {"conv_ms_per_step": round(conv_s * 1e3, 4), "avg_launch_us": round(conv_s / max(n_conv, 1) * 1e6, 2),
+                                  "timing": f"HIP events on the plan's stream around the conv launches, one batch in flight, mean of {n_excl} steps right after the timed region"},
+                       "pipelined": {"batches_in_flight": depth, "ms_per_step": round(step_s * 1e3, 4), "frac_of_per_layer_bound": round(bound_s / step_s, 4),
+                                     "tflops": round(flops_step / step_s / 1e12, 2)},
+                       "other_kernels": {"letterbox": {"ms": round(mean(excl["pre"]), 4)} if excl["pre"] else None, "postprocess": {"ms": round(mean(excl["post"]), 4)} if excl["post"] else None}}
     if not args.no_cpu_baseline:
         sd_cpu = {k: v.float().cpu() for k, v in model.state_dict().items()}
         cp = conditioned_parity(args, dev, fp32_only=True)
@@ -736,6 +771,47 @@ def main():
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     elapsed, host_enqueue_ms, dets = reps[order[len(order) // 2]]
     rep_ips = [round(world * args.batch * args.steps / r[0], 1) for r in reps]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, reps[-1][2])
+    step_s = elapsed / args.steps
+    ips = world * args.batch * args.steps / elapsed
+    out = None
+    if rank == 0:
+        workload = (f"{args.arch} {args.dtype} bs={args.batch}/GPU {args.size}x{args.size} "
+                    + ("dynamic-shape letterbox (8 cycled sizes, SURVEY 8d) -> " if args.shapes == "dynamic" else "fixed-size stream (letterbox = identity: the stem reads the planar images) -> ")
+                    + f"backbone+PAN+head+decode+NMS HIP path (BASELINE configs[{dict(c1=0, c2=1, c3=2, c5=4)[args.config]}])")
+        out = {
+            "metric": "images/sec at 640x640 (bs=32) yolov5s" if args.config == "c2" else f"images/sec at {args.size}x{args.size} (bs={args.batch}) {args.arch}",
+            "value": round(ips, 2),
+            "unit": "images/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(step_s * 1e3, 4),
+            "repeats": {"n": len(reps), "images_per_s": rep_ips if len(rep_ips) <= 12 else rep_ips[:4] + ["..."] + rep_ips[-4:], "median": round(ips, 2), "min": min(rep_ips), "max": max(rep_ips),
+                        "spread_pct": round(100.0 * (max(rep_ips) - min(rep_ips)) / max(ips, 1e-9), 2),
+                        "p10_p90": [sorted(rep_ips)[len(rep_ips) // 10], sorted(rep_ips)[(9 * len(rep_ips)) // 10 - (1 if len(rep_ips) >= 10 else 0)]],
+                        "timed_seconds_total": round(sum(r[0] for r in reps), 3),
+                        "note": "the timed region (exactly `steps` steps, barrier + synchronize on both sides) run back to back until >= --min-seconds of work; value / ms_per_step are the median region"},
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": workload, "score_thresh": args.score_thresh, "nms_thresh": 0.45, "detections_per_img": 300,
+                       "weights": f"seeded synthetic (workloads/synth.py, head_gain {args.head_gain})", "parallelism": f"dp{world} (one shard per rank, slab all-gather)",
+                       "gather_second_rounds_rank0": second_rounds[0], "host_enqueue_ms_per_step_rank0": round(host_enqueue_ms, 4),
+                       "submit_path_of_timed_regions": ("ymi_plan_begin + ymi_plan_submit (the product's default: two C-ABI calls per batch, conv stack and post-process as one graph launch each)"
+                                                        if world == 1 else "torch-level sequence (the slab all-gather is enqueued from Python behind each batch)"),
+                       "canvas": [e.x.h, e.x.w], "detections_per_step_rank0": int(sum(len(d["scores"]) for d in dets)),
+                       "conv_tiles": "pinned table yolort_amd/data/tiles_gfx950.json" if not e.plan.autotune else "autotuned at plan build"},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # one more region, NOT part of `value`: event pairs recorded on the launching streams around each batch's conv / post-process launches while batches overlap (the
     # brackets take the torch-level submit sequence: 0.05 ms more host time per batch than the default path -- which is why they are no longer inside the timed regions)
     yolo.bracket = {"pre": ([], []), "conv": ([], []), "post": ([], [])}
@@ -843,9 +919,7 @@ def main():
         bound_meas_s = sum(max(f / MFMA_MEASURED, b / HBM_MEASURED) for f, b in per_layer)
         conv_s = mean(excl["conv"]) * 1e-3                 # serial duration of the conv launches of one step
         conv_s_region = mean(region["conv"]) * 1e-3
-        step_s = elapsed / args.steps
         achieved = bytes_step / conv_s / 1e9 if conv_s > 0 else 0.0
-        ips = world * args.batch * args.steps / elapsed
         # HBM traffic of the conv launches from the committed PMC passes (rocprofv3 cannot run inside this process):
         # per launch like `achieved`; only quoted for the workload it was measured on
         traffic = None
@@ -870,68 +944,40 @@ def main():
             kernels["postprocess (select_prefix + sort_image + nms_segments + gather_topk)"] = {
                 "ms": round(ms, 4), "candidates_per_step": n_cand, "records_sorted_per_step": n_cand_sorted, "algorithmic_bytes": pbytes, "achieved_GBps": round(pbytes / ms / 1e6, 1),
                 "frac_of_hbm_peak": round(pbytes / (ms * 1e-3) / HBM_PEAK, 5), "note": "latency-bound (per-image sort + greedy NMS), not bandwidth-bound"}
-        workload = (f"{args.arch} {args.dtype} bs={args.batch}/GPU {args.size}x{args.size} "
-                    + ("dynamic-shape letterbox (8 cycled sizes, SURVEY 8d) -> " if args.shapes == "dynamic" else "fixed-size stream (letterbox = identity: the stem reads the planar images) -> ")
-                    + f"backbone+PAN+head+decode+NMS HIP path (BASELINE configs[{dict(c1=0, c2=1, c3=2, c5=4)[args.config]}])")
-        out = {
-            "metric": "images/sec at 640x640 (bs=32) yolov5s" if args.config == "c2" else f"images/sec at {args.size}x{args.size} (bs={args.batch}) {args.arch}",
-            "value": round(ips, 2),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_s * 1e3, 4),
-            "repeats": {"n": len(reps), "images_per_s": rep_ips if len(rep_ips) <= 12 else rep_ips[:4] + ["..."] + rep_ips[-4:], "median": round(ips, 2), "min": min(rep_ips), "max": max(rep_ips),
-                        "spread_pct": round(100.0 * (max(rep_ips) - min(rep_ips)) / max(ips, 1e-9), 2),
-                        "p10_p90": [sorted(rep_ips)[len(rep_ips) // 10], sorted(rep_ips)[(9 * len(rep_ips)) // 10 - (1 if len(rep_ips) >= 10 else 0)]],
-                        "timed_seconds_total": round(sum(r[0] for r in reps), 3),
-                        "note": "the timed region (exactly `steps` steps, barrier + synchronize on both sides) run back to back until >= --min-seconds of work; value / ms_per_step are the median region"},
-            "serial_images_per_s": round(serial_ips, 1),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": workload, "score_thresh": args.score_thresh, "nms_thresh": 0.45, "detections_per_img": 300,
-                       "weights": f"seeded synthetic (workloads/synth.py, head_gain {args.head_gain})", "parallelism": f"dp{world} (one shard per rank, slab all-gather)",
-                       "gather_second_rounds_rank0": second_rounds[0], "host_enqueue_ms_per_step_rank0": round(host_enqueue_ms, 4),
-                       "submit_path_of_timed_regions": ("ymi_plan_begin + ymi_plan_submit (the product's default: two C-ABI calls per batch, conv stack and post-process as one graph launch each)"
-                                                        if world == 1 else "torch-level sequence (the slab all-gather is enqueued from Python behind each batch)"),
-                       "serving_mode_rank0": serving,
-                       "canvas": [e.x.h, e.x.w], "detections_per_step_rank0": int(sum(len(d["scores"]) for d in dets)),
-                       "candidates_per_step_rank0": n_cand, "records_sorted_per_step_rank0": n_cand_sorted, "conv_tiles": "pinned table yolort_amd/data/tiles_gfx950.json" if not e.plan.autotune else "autotuned at plan build"},
-            # `frac` is the PER-LAYER fraction SURVEY.md 8d prescribes (sum over the conv launches of max(flops / MFMA peak, bytes / HBM peak),
-            # divided by the measured conv time) in the SERIAL regime; achieved / peak / frac_hbm are the plain bytes-over-time view of the
-            # same measurement.  The two regimes are spelled out: `serial` = one batch in flight (what rocprofv3's kernel durations add up
-            # to); `pipelined` = the timed region, `batches_in_flight` batches on separate streams filling each other's launch gaps and
-            # partial waves -- the regime `value` is measured in (its step time also holds the letterbox / post-process launches).
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0,
-                         "frac_definition": "per-layer bound (SURVEY 8d): sum_l max(flops_l / 2.5 PFLOP/s, bytes_l / 8 TB/s) / measured serial conv time; 49 of 60 yolov5s layers are HBM-bound",
-                         "frac_hbm": round(achieved * 1e9 / HBM_PEAK, 4),
-                         "against_measured_ceilings": {"mfma_tflops": MFMA_MEASURED / 1e12, "hbm_gbps": HBM_MEASURED / 1e9, "per_layer_bound_ms": round(bound_meas_s * 1e3, 4),
-                                                       "frac": round(bound_meas_s / conv_s, 4) if conv_s > 0 else 0.0,
-                                                       "note": "the same per-layer bound priced at what this chip was measured to deliver on these shapes (vendor GEMM <= 0.99 PFLOP/s, "
-                                                               "copy 5 TB/s; shader clock 1.58 GHz under LDS + MFMA load) -- context, not the contract's fraction"},
-                         "traffic": traffic,
-                         "kernel": "conv family: c3_tile_kernel (the C3 strip kernel: 8 of the 29 launches, 39 % of the time), conv_igemm_v2_kernel, conv_igemm8_kernel, conv_halo8_kernel, conv3x3_rs_kernel, c3_fused32_kernel, stem_body1_fused_kernel, conv_head_decode_group_kernel (all conv launches of one step)",
-                         "shader_clock_mhz_measured": clock_mhz,
-                         "peaks_priced_at": "2.4 GHz (2.5 PFLOP/s dense fp16 / bf16) and 8 TB/s, as the contract demands; the chip sustains the measured clock under this load",
-                         "launches_per_step": n_conv, "algorithmic_bytes_per_step": bytes_step, "algorithmic_bytes_per_launch": round(bytes_step / max(n_conv, 1)),
-                         "algorithmic_flops_per_step": flops_step, "per_layer_bound_ms": round(bound_s * 1e3, 4),
-                         "serial": {"conv_ms_per_step": round(conv_s * 1e3, 4), "avg_launch_us": round(conv_s / max(n_conv, 1) * 1e6, 2),
-                                    "frac_of_per_layer_bound": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0, "frac_of_hbm_peak": round(achieved * 1e9 / HBM_PEAK, 4),
-                                    "tflops": round(flops_step / conv_s / 1e12, 2) if conv_s > 0 else 0.0,
-                                    "timing": f"HIP events on the plan's stream around the conv launches, one batch in flight, mean of {n_excl} steps right after the timed region"},
-                         "pipelined": {"batches_in_flight": depth, "ms_per_step": round(step_s * 1e3, 4),
-                                       "frac_of_per_layer_bound": round(bound_s / step_s, 4), "frac_of_hbm_peak": round(bytes_step / step_s / HBM_PEAK, 4),
-                                       "tflops": round(flops_step / step_s / 1e12, 2),
-                                       "conv_bracket_ms": round(conv_s_region * 1e3, 4),
-                                       "conv_bracket_submit_path": "torch-level sequence with event pairs, in a region of its own that is not part of `value`",
-                                       "note": "per-layer bound / ms_per_step of the timed region: a LOWER bound on the conv stack's fraction there (the step also holds the "
-                                               "post-process launches); conv_bracket_ms = event brackets around one batch's conv launches while they share the GPU with its neighbours' kernels"},
-                         "other_kernels": kernels},
-        }
+        out["serial_images_per_s"] = round(serial_ips, 1)
+        out["config"].update({"gather_second_rounds_rank0": second_rounds[0], "serving_mode_rank0": serving,
+                              "candidates_per_step_rank0": n_cand, "records_sorted_per_step_rank0": n_cand_sorted})
+        # `frac` is the PER-LAYER fraction SURVEY.md 8d prescribes (sum over the conv launches of max(flops / MFMA peak, bytes / HBM peak),
+        # divided by the measured conv time) in the SERIAL regime; achieved / peak / frac_hbm are the plain bytes-over-time view of the
+        # same measurement.  The two regimes are spelled out: `serial` = one batch in flight (what rocprofv3's kernel durations add up
+        # to); `pipelined` = the timed region, `batches_in_flight` batches on separate streams filling each other's launch gaps and
+        # partial waves -- the regime `value` is measured in (its step time also holds the letterbox / post-process launches).
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                           "frac": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0,
+                           "frac_definition": "per-layer bound (SURVEY 8d): sum_l max(flops_l / 2.5 PFLOP/s, bytes_l / 8 TB/s) / measured serial conv time; 49 of 60 yolov5s layers are HBM-bound",
+                           "frac_hbm": round(achieved * 1e9 / HBM_PEAK, 4),
+                           "against_measured_ceilings": {"mfma_tflops": MFMA_MEASURED / 1e12, "hbm_gbps": HBM_MEASURED / 1e9, "per_layer_bound_ms": round(bound_meas_s * 1e3, 4),
+                                                         "frac": round(bound_meas_s / conv_s, 4) if conv_s > 0 else 0.0,
+                                                         "note": "the same per-layer bound priced at what this chip was measured to deliver on these shapes (vendor GEMM <= 0.99 PFLOP/s, "
+                                                                 "copy 5 TB/s; shader clock 1.58 GHz under LDS + MFMA load) -- context, not the contract's fraction"},
+                           "traffic": traffic,
+                           "kernel": "conv family: c3_tile_kernel (the C3 strip kernel: 8 of the 29 launches, 39 % of the time), conv_igemm_v2_kernel, conv_igemm8_kernel, conv_halo8_kernel, conv3x3_rs_kernel, c3_fused32_kernel, stem_body1_fused_kernel, conv_head_decode_group_kernel (all conv launches of one step)",
+                           "shader_clock_mhz_measured": clock_mhz,
+                           "peaks_priced_at": "2.4 GHz (2.5 PFLOP/s dense fp16 / bf16) and 8 TB/s, as the contract demands; the chip sustains the measured clock under this load",
+                           "launches_per_step": n_conv, "algorithmic_bytes_per_step": bytes_step, "algorithmic_bytes_per_launch": round(bytes_step / max(n_conv, 1)),
+                           "algorithmic_flops_per_step": flops_step, "per_layer_bound_ms": round(bound_s * 1e3, 4),
+                           "serial": {"conv_ms_per_step": round(conv_s * 1e3, 4), "avg_launch_us": round(conv_s / max(n_conv, 1) * 1e6, 2),
+                                      "frac_of_per_layer_bound": round(bound_s / conv_s, 4) if conv_s > 0 else 0.0, "frac_of_hbm_peak": round(achieved * 1e9 / HBM_PEAK, 4),
+                                      "tflops": round(flops_step / conv_s / 1e12, 2) if conv_s > 0 else 0.0,
+                                      "timing": f"HIP events on the plan's stream around the conv launches, one batch in flight, mean of {n_excl} steps right after the timed region"},
+                           "pipelined": {"batches_in_flight": depth, "ms_per_step": round(step_s * 1e3, 4),
+                                         "frac_of_per_layer_bound": round(bound_s / step_s, 4), "frac_of_hbm_peak": round(bytes_step / step_s / HBM_PEAK, 4),
+                                         "tflops": round(flops_step / step_s / 1e12, 2),
+                                         "conv_bracket_ms": round(conv_s_region * 1e3, 4),
+                                         "conv_bracket_submit_path": "torch-level sequence with event pairs, in a region of its own that is not part of `value`",
+                                         "note": "per-layer bound / ms_per_step of the timed region: a LOWER bound on the conv stack's fraction there (the step also holds the "
+                                                 "post-process launches); conv_bracket_ms = event brackets around one batch's conv launches while they share the GPU with its neighbours' kernels"},
+                           "other_kernels": kernels}
         if dyn is not None:
             out["roofline"]["other_kernels"]["dynamic_shape_stream"] = dyn
             # secondary value: the same model on the dynamic-shape stream -- every batch runs the letterbox launch (the headline stream is letterbox-free: its

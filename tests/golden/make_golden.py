@@ -3,6 +3,7 @@
 
 usage: python tests/golden/make_golden.py
 """
+import hashlib
 import json
 import os
 import sys
@@ -536,7 +537,58 @@ def bench_golden(config="c2"):
     np.savez_compressed(os.path.join(HERE, f"bench_{config}.npz"), **out)
 
 
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The r3.1 / r4.0 releases as goldens: the reference's `model.backbone(x)` on the seeded weights of
+# tests/test_oracle_golden.py::test_legacy_backbones_equal_the_live_reference_bit_for_bit (the reference's own initialisation under
+# torch.manual_seed(3) -- this package's models initialise identically -- then BatchNorm affine / statistics and the input from
+# Generator(4)), and the state_dict layout (keys, shapes, dtypes) of its s / m / l models for tests/test_host_logic.py.
+# ---------------------------------------------------------------------------------------------------------------------------
+LEGACY_ARCHS = ["yolov5_darknet_pan_s_r40", "yolov5_darknet_pan_s_r31", "yolov5_darknet_pan_m_r40", "yolov5_darknet_pan_m_r31"]
+
+
+def legacy_golden():
+    out = {}
+    for arch in LEGACY_ARCHS:
+        torch.manual_seed(3)
+        m = yolort.models.yolo.__dict__[arch]().eval()
+        g = torch.Generator().manual_seed(4)
+        with torch.no_grad():
+            for k, v in m.state_dict().items():
+                if k.endswith("running_mean"):
+                    v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+                elif k.endswith("running_var"):
+                    v.copy_(torch.rand(v.shape, generator=g) * 0.5 + 0.75)
+                elif k.endswith("bn.weight"):
+                    v.copy_(torch.rand(v.shape, generator=g) * 0.5 + 0.75)
+                elif k.endswith("bn.bias"):
+                    v.copy_(torch.randn(v.shape, generator=g) * 0.1)
+            x = torch.rand(2, 3, 96, 128, generator=g)
+            want = m.backbone(x)
+        for i, t in enumerate(want):
+            a = t.contiguous().numpy().astype(np.float32) + np.float32(0.0)   # -0.0 -> +0.0: equal digests <=> torch.equal
+            out[f"{arch}_{i}"] = {"shape": list(a.shape), "sha256": hashlib.sha256(a.tobytes()).hexdigest(), "sum": float(a.astype(np.float64).sum()),
+                                  "first": [float(v) for v in a.ravel()[:8]]}
+        print(arch, [tuple(t.shape) for t in want])
+    with open(os.path.join(HERE, "legacy_backbones.json"), "w") as f:
+        json.dump({"what": "the UNMODIFIED reference's `model.backbone(x)` outputs (float32, -0.0 stored as +0.0): sha256 of the raw bytes, shape, float64 sum and first values",
+                   "outputs": out}, f, indent=1)
+    layout = {}
+    for tag in ("r40", "r31"):
+        for size in ("s", "m", "l"):
+            sd = yolort.models.yolo.__dict__[f"yolov5_darknet_pan_{size}_{tag}"]().state_dict()
+            rows = [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in sd.items()]
+            canon = "".join(f"{k} {tuple(shape)} {dtype}\n" for k, shape, dtype in rows)
+            layout[f"{size}_{tag}"] = {"n": len(rows), "sha256": hashlib.sha256(canon.encode()).hexdigest(), "first": rows[:3], "last": rows[-3:]}
+    with open(os.path.join(HERE, "legacy_state_dicts.json"), "w") as f:
+        json.dump({"what": "state_dict layout of the UNMODIFIED reference's r3.1 / r4.0 models: sha256 of the lines `<key> <shape tuple> <dtype>` in state_dict order, "
+                           "their count, the first and last rows", "models": layout}, f, indent=1)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "legacy":   # usage: legacy
+        legacy_golden()
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bench":   # usage: bench [config]
         bench_golden(*(sys.argv[2:3] or ["c2"]))
         sys.exit(0)

@@ -1,5 +1,6 @@
+REPO="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace -d /tmp/prof_n -o r -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 4 --no-cpu-baseline > /tmp/b_n.log 2>&1
+timeout 400 rocprofv3 --kernel-trace -d /tmp/prof_n -o r -- python "$REPO/bench.py" --steps 20 --warmup 4 --no-cpu-baseline --full > /tmp/b_n.log 2>&1
 python - <<'PY'
 import sqlite3, glob
 db=glob.glob('/tmp/prof_n/**/*.db', recursive=True)[0]

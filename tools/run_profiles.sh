@@ -12,7 +12,7 @@ echo "== tests" ; date
 timeout 1800 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider > $O/tests.log 2>&1; tail -4 $O/tests.log
 echo "== bench" ; date
 for c in c2 c3 c5; do
-  timeout 600 python bench.py --config $c > $O/bench_$c.log 2>&1; grep '^{"metric' $O/bench_$c.log | tail -1 > $O/bench_$c.json; cut -c1-160 $O/bench_$c.json
+  timeout 600 python bench.py --config $c --full > $O/bench_$c.log 2>&1; grep '^{"metric' $O/bench_$c.log | tail -1 > $O/bench_$c.json; cut -c1-160 $O/bench_$c.json
 done
 echo "== rocprof" ; date
 for cfg in c2 c3 c5; do
