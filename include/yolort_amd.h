@@ -333,7 +333,9 @@ int ymi_conv_head_decode_group(const ymi_conv_desc* convs, int n_levels, const y
 
 /* Stand-alone class-aware NMS on caller-provided candidates of ONE image (kept indices in
  * score-descending stable order, like torchvision.ops.batched_nms called at box_head.py:422).
- * boxes (n,4) fp32 xyxy, scores (n) fp32, labels (n) int32; keep_out (n) int32, count_out int32[1]. */
+ * boxes (n,4) fp32 xyxy, scores (n) fp32, labels (n) int32; keep_out (n) int32, count_out int32[1].
+ * Scores may be any non-NaN floats (negative, +-0 -- a tie --, +-inf, subnormal); NaN scores / coordinates are outside
+ * the contract.  n < 2^20. */
 int64_t ymi_nms_ws_bytes(int n);
 int ymi_batched_nms(const float* boxes, const float* scores, const int32_t* labels, int n, float nms_thresh,
                     int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);

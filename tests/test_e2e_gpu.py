@@ -149,7 +149,8 @@ def test_yolov5s_640_vs_oracle(dev):
 
 
 @pytest.mark.parametrize("arch,num_classes,dtype", [("yolov5_darknet_pan_s_r60", 80, torch.float16), ("yolov5_darknet_pan_n_r60", 20, torch.bfloat16),
-                                                    ("yolov5_darknet_pan_n_r60", 3, torch.float16), ("yolov5_darknet_pan_n_r60", 100, torch.float16)])
+                                                    ("yolov5_darknet_pan_n_r60", 3, torch.float16), ("yolov5_darknet_pan_n_r60", 100, torch.float16)]
+                         + [("yolov5_darknet_pan_n_r60", nc, torch.float16) for nc in (1, 27, 28, 59, 60, 123)])   # 1: one label bit; the others: both sides of every anchor padding (K = 32 / 33, 64 / 65, 128)
 def test_fused_head_decode_equals_unfused(dev, arch, num_classes, dtype):
     """ymi_conv_head_decode (decode + threshold in the head conv's epilogue) must produce exactly the records
     the stored-logits path produces: same detections bit for bit, same candidate count; K = num_classes + 5 covers
@@ -169,6 +170,30 @@ def test_fused_head_decode_equals_unfused(dev, arch, num_classes, dtype):
         for k in ("boxes", "scores", "labels"):
             assert torch.equal(a[k], b[k]), f"fused / unfused head disagree on {k}"
     assert sum(len(d["scores"]) for d in outs[0]) > 0
+
+
+def test_head_of_124_classes_runs_through_stored_logits(dev):
+    """num_classes = 124 (K = 129 rows per anchor) is the first count the fused head refuses: the model must store the fp32 head logits and post-process them,
+    and its detections must be what ops.postprocess_logits returns for exactly those logits"""
+    from workloads.synth import synth_images
+    from yolort_amd.ops import postprocess_logits
+    nc = 124
+    m = _model("yolov5_darknet_pan_n_r60", dev, torch.float16, num_classes=nc, score_thresh=0.2, nms_thresh=0.45)
+    x = torch.stack([im for im in synth_images(5, 320, 320, seed=5)]).to(dev).half()
+    assert m.model.fuse_head_decode
+    out = m.model(x)
+    e = next(iter(m.model._entries.values()))
+    assert e.logits is not None, "the fused head took 124 classes"
+    heads = []
+    for v in e.logits:
+        t = v.as_tensor()
+        heads.append(t.reshape(t.shape[0], t.shape[1], t.shape[2], 3, nc + 5).permute(0, 3, 1, 2, 4).contiguous())
+    ag, pp = m.model.anchor_generator, m.model.post_process
+    want = postprocess_logits(heads, [float(s) for s in ag.strides], ag.anchor_grids, nc, float(pp.score_thresh), float(pp.nms_thresh), int(pp.detections_per_img))
+    assert sum(len(d["scores"]) for d in out) > 0
+    for a, b in zip(out, want):
+        for k in ("boxes", "scores", "labels"):
+            assert torch.equal(a[k], b[k]), f"model / postprocess_logits disagree on {k}"
 
 
 @pytest.mark.parametrize("k_det", [300, 1500])

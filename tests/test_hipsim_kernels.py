@@ -20,6 +20,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _post_cases
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DIR = os.path.join(ROOT, "tests", "hipsim")
 
@@ -838,6 +840,43 @@ def test_batched_nms_bit_exact_vs_oracle(sim, n, ncls, ties):
     np.testing.assert_array_equal(keep[: int(count[0])].astype(np.int64), ref)
 
 
+def _sim_nms(sim, case):
+    """ymi_batched_nms on the simulator with a DIRTY workspace and pre-filled outputs -> (rc, keep, count)"""
+    n = len(case["scores"])
+    labels = case["labels"].astype(np.int32)
+    keep, count = np.full(max(n, 1), -7, np.int32), np.full(1, -7, np.int32)
+    ws = np.full(int(sim.ymi_nms_ws_bytes(n)), 0x7f, np.uint8)
+    rc = sim.ymi_batched_nms(case["boxes"].ctypes.data, case["scores"].ctypes.data, labels.ctypes.data, n, C.c_float(case["thr"]), keep.ctypes.data, count.ctypes.data,
+                             ws.ctypes.data, ws.size, None)
+    return rc, keep, count
+
+
+@pytest.mark.parametrize("name", _post_cases.NMS_CASES)
+def test_batched_nms_adversarial_vs_oracle(sim, name):
+    """The stand-alone NMS on inputs chosen against it (tests/_post_cases.py), same sizes as the GPU form of this test (tests/test_ops_gpu.py; nothing is shrunk:
+    the 2 700-box grids take ~20 s each here): scores of both signs, signed zeros, infinities and subnormals (the sort key must order ALL floats, -0.0 == +0.0 a tie
+    broken by index), segments that keep more than NMS_KCAP boxes (read back from the spill area), zero / negative areas and IoU == threshold under strict >,
+    coordinates near +-1e6, segments of 63..129 candidates around the 64-lane step, 2..4097 equal scores (radix pass counts, stability), one class per box.
+    Kept indices equal the oracle's, element for element; every case first proves from the oracle's result that it is not vacuous."""
+    from oracle import yolov5_oracle as O
+    case = _post_cases.nms_case(name)
+    ref = O.batched_nms(torch.from_numpy(case["boxes"]), torch.from_numpy(case["scores"]), torch.from_numpy(case["labels"]), case["thr"]).numpy()
+    per_class = _post_cases.assert_nms_case_is_not_vacuous(name, case, ref)
+    print(f"{name}: n={len(case['scores'])} classes={len(per_class)} oracle keeps {len(ref)} (largest class {per_class.max()})")
+    rc, keep, count = _sim_nms(sim, case)
+    _check(sim, rc)
+    np.testing.assert_array_equal(keep[: int(count[0])].astype(np.int64), ref)
+
+
+def test_batched_nms_refuses_two_to_the_twenty_candidates(sim):
+    """candidate indices share a 32-bit word with 12 bits of class: n = 2^20 is refused by name, before anything is launched (outputs untouched); 2^20 - 1 is the limit"""
+    n = 1 << 20
+    case = dict(boxes=np.zeros((n, 4), np.float32), scores=np.zeros(n, np.float32), labels=np.zeros(n, np.int64), thr=0.45)
+    rc, keep, count = _sim_nms(sim, case)
+    assert rc != 0 and "out of range" in sim.sim_last_error().decode() and str(n - 1) in sim.sim_last_error().decode()
+    assert int(count[0]) == -7 and (keep == -7).all()
+
+
 @pytest.mark.parametrize("thr,k,saturated,cap0", [(0.3, 300, False, 4096), (0.05, 50, False, 4096), (0.3, 300, True, 4096), (0.02, 300, False, 131072), (0.3, 300, True, 131072),
                                                  (0.02, 300, "mixed", 131072)])
 def test_postprocess_vs_oracle(sim, thr, k, saturated, cap0):
@@ -930,6 +969,99 @@ def test_postprocess_vs_oracle(sim, thr, k, saturated, cap0):
         gain, px, py = rescale[i].tolist()
         want = (r["boxes"] - torch.tensor([px, py, px, py])) / gain
         np.testing.assert_allclose(boxes[i, :c].numpy(), want.numpy(), rtol=1e-5, atol=2e-4)
+
+
+def _sim_post(sim, heads, strides, anchors, nc, thr, k, cap0=4096, fill=0.0):
+    """ymi_postprocess on the simulator from reference-layout head outputs under the host protocol of yolort_amd/ops.py (grow the capacity / take the exact full pass
+    and redo).  Outputs are pre-filled with `fill`, the workspace is dirty.  -> (rc, dict of the output arrays) of the last pass"""
+    from yolort_amd._lib import PostDesc
+    n, kk = heads[0].shape[0], nc + 5
+    shapes = [(ho.shape[2], ho.shape[3]) for ho in heads]
+    logits = []
+    for ho in heads:
+        cs = (3 * kk + 3) // 4 * 4
+        t = torch.zeros(n, ho.shape[2], ho.shape[3], cs, dtype=torch.float32)
+        t[..., : 3 * kk] = ho.permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * kk)
+        logits.append(t)
+    total_anchors = sum(3 * h * w for h, w in shapes)
+    cap, flags = cap0, 0
+    while True:
+        out = dict(boxes=torch.full((n, k, 4), fill), scores=torch.full((n, k), fill), labels=torch.full((n, k), int(fill), dtype=torch.int64),
+                   count=torch.full((n,), int(fill), dtype=torch.int32), status=torch.full((8,), int(fill), dtype=torch.int32))
+        ws = torch.full((int(sim.ymi_postprocess_ws_bytes(n, total_anchors, cap)),), 0x7f, dtype=torch.uint8)
+        d = PostDesc()
+        for i, (h, w) in enumerate(shapes):
+            d.lh[i], d.lw[i], d.stride[i] = h, w, float(strides[i])
+            for j in range(6):
+                d.anchors[i][j] = float(anchors[i][j])
+            d.logits[i], d.lcstride[i] = logits[i].data_ptr(), logits[i].shape[3]
+        d.num_levels, d.n, d.num_classes = len(shapes), n, nc
+        d.score_thresh, d.nms_thresh, d.detections_per_img = thr, 0.45, k
+        d.out_boxes, d.out_scores, d.out_labels, d.out_count = out["boxes"].data_ptr(), out["scores"].data_ptr(), out["labels"].data_ptr(), out["count"].data_ptr()
+        d.status, d.ws, d.ws_bytes, d.cand_cap, d.flags = out["status"].data_ptr(), ws.data_ptr(), ws.numel(), cap, flags
+        rc = sim.ymi_postprocess(C.byref(d), None)
+        st = out["status"].tolist()
+        if rc != 0 or st[1] == 0:
+            return rc, out
+        if not st[1] & 1:
+            flags = 1   # YMI_POST_EXACT_FULL
+            continue
+        need = max(st[0], st[3] * n)
+        cap = max(int(need * 1.25) + 1024, 2 * cap)
+        cap = n * (1 << ((cap + n - 1) // n - 1).bit_length())
+
+
+def _assert_post_equals_oracle(out, ref, k, fill):
+    """counts, labels, order exact; scores / boxes to the rounding of expf (the constants of test_postprocess_vs_oracle); nothing written past the counts"""
+    for i, r in enumerate(ref):
+        c = int(out["count"][i])
+        assert c == len(r["scores"]), (i, c, len(r["scores"]))
+        np.testing.assert_array_equal(out["labels"][i, :c].numpy(), r["labels"].numpy())
+        np.testing.assert_allclose(out["scores"][i, :c].numpy(), r["scores"].numpy(), rtol=2e-6, atol=1e-7)
+        np.testing.assert_allclose(out["boxes"][i, :c].numpy(), r["boxes"].numpy(), rtol=1e-5, atol=1e-4)
+        assert (out["scores"][i, c:] == fill).all() and (out["labels"][i, c:] == int(fill)).all() and (out["boxes"][i, c:] == fill).all(), f"image {i}: slots past the count were written"
+
+
+@pytest.mark.parametrize("nc", _post_cases.POST_CLASS_COUNTS)
+def test_postprocess_vs_oracle_class_counts(sim, nc):
+    """decode + threshold + sort + NMS + top-k against O.decode + O.postprocess at the class counts where the decode changes shape: 1 (one label bit, the smallest
+    legal count), 27 / 28 (both sides of an anchor padding), 80 / 81 (255 channels = one float4 pass per pixel / the first count that needs two), 91, 124 (the first the
+    fused head refuses), 166 (3 * 171 = 513 channels: the first pixel wider than the 512-record wave buffer), 200 and 601 (a pixel passes 600 / 1803 records: the buffer is
+    flushed in the middle of a pixel).  Three images on the levels test_postprocess_vs_oracle uses here ((10, 12), (5, 6), (3, 3): a quarter of the GPU test's pixels);
+    per class count a top-k cut at 7 with thousands of survivors and a batch whose middle image has no candidate; the other runs of the GPU test (cuts at 1 / 50 / 300,
+    the threshold 0.3 on the full batch, a batch without any candidate) at nc = 2 only: a run costs ~15 s here whatever its size, the full list would take 20 minutes."""
+    from oracle import yolov5_oracle as O
+    shapes = [(10, 12), (5, 6), (3, 3)]
+    strides, anchors = O.anchors_for(3)
+    refs = {}
+    for variant, thr, k, truncates in _post_cases.post_runs(nc, sum(3 * h * w for h, w in shapes), lean=True):
+        heads = _post_cases.post_heads(nc, shapes, empty=_post_cases.POST_EMPTY[variant])
+        if (variant, thr) not in refs:
+            pred = O.decode(heads, strides, anchors)
+            refs[variant, thr] = (pred, O.postprocess(pred, thr, 0.45, 1 << 30))
+        pred, full = refs[variant, thr]
+        survivors, hot = _post_cases.assert_post_case_is_not_vacuous(nc, variant, thr, k, truncates, pred, shapes, full)
+        print(f"nc={nc} {variant} thr={thr} k={k}: candidates {_post_cases.oracle_candidates_per_anchor(pred, thr).sum(1).tolist()} survivors {survivors} hottest pixel {hot}")
+        rc, out = _sim_post(sim, heads, strides, anchors, nc, thr, k, cap0=3 * 8192, fill=-3.0)
+        _check(sim, rc)
+        _assert_post_equals_oracle(out, [{key: v[:k] for key, v in r.items()} for r in full], k, -3.0)
+
+
+def test_postprocess_batch_size_limit(sim):
+    """1 025 images are refused by name BEFORE anything runs -- status words and outputs keep their pattern -- and 1 024 images (one 2 x 2 level, two classes) equal the oracle"""
+    from oracle import yolov5_oracle as O
+    strides, anchors = [8], [O.ANCHORS_P5[0]]
+    g = torch.Generator().manual_seed(1025)
+    rc, out = _sim_post(sim, [torch.randn(1025, 3, 1, 1, 7, generator=g) + 1.0], strides, anchors, 2, 0.3, 10, cap0=1025 * 64, fill=-3.0)
+    assert rc != 0 and "1024" in sim.sim_last_error().decode(), sim.sim_last_error().decode()
+    for key, v in out.items():
+        assert (v == -3).all(), f"{key} was written although the batch was refused"
+    heads = [torch.randn(1024, 3, 2, 2, 7, generator=g) + 1.0]
+    ref = O.postprocess(O.decode(heads, strides, anchors), 0.3, 0.45, 10)
+    rc, out = _sim_post(sim, heads, strides, anchors, 2, 0.3, 10, cap0=1024 * 64, fill=-3.0)
+    _check(sim, rc)
+    _assert_post_equals_oracle(out, ref, 10, -3.0)
+    assert int(out["count"].sum()) > 1024
 
 
 @pytest.mark.parametrize("dtype,nc", [(torch.float16, 80), (torch.bfloat16, 11)])

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _post_cases
+
 pytestmark = pytest.mark.gpu
 
 
@@ -881,6 +883,33 @@ def test_batched_nms_bit_exact(dev, n, ncls, ties):
     np.testing.assert_array_equal(got, ref)
 
 
+@pytest.mark.parametrize("name", _post_cases.NMS_CASES)
+def test_batched_nms_adversarial_vs_oracle(dev, name):
+    """The stand-alone NMS on inputs chosen against it (tests/_post_cases.py; the same cases run on the CPU simulator in tests/test_hipsim_kernels.py): scores of both
+    signs, signed zeros, infinities and subnormals (the sort key must order ALL floats, -0.0 == +0.0 a tie broken by index), segments that keep more than NMS_KCAP = 384
+    boxes (a wave reads back the boxes it spilled to HBM -- only hardware says whether it sees them), zero / negative areas and IoU == threshold under strict >,
+    coordinates near +-1e6, segments of 63..129 candidates around the 64-lane step, 2..4097 equal scores (radix pass counts, stability), one class per box.
+    Kept indices equal the oracle's, element for element; every case first proves from the oracle's result that it is not vacuous."""
+    from oracle import yolov5_oracle as O
+    from yolort_amd.ops import batched_nms
+    case = _post_cases.nms_case(name)
+    boxes, scores, labels = torch.from_numpy(case["boxes"]), torch.from_numpy(case["scores"]), torch.from_numpy(case["labels"])
+    ref = O.batched_nms(boxes, scores, labels, case["thr"]).numpy()
+    per_class = _post_cases.assert_nms_case_is_not_vacuous(name, case, ref)
+    print(f"{name}: n={len(case['scores'])} classes={len(per_class)} oracle keeps {len(ref)} (largest class {per_class.max()})")
+    got = batched_nms(boxes.to(dev), scores.to(dev), labels.to(dev), case["thr"]).cpu().numpy()
+    np.testing.assert_array_equal(got, ref)
+
+
+def test_batched_nms_refuses_two_to_the_twenty_candidates(dev):
+    """candidate indices share a 32-bit word with 12 bits of class: n = 2^20 is refused by name"""
+    from yolort_amd._lib import YmiError
+    from yolort_amd.ops import batched_nms
+    n = 1 << 20
+    with pytest.raises(YmiError, match=f"out of range.*{n - 1}"):
+        batched_nms(torch.zeros(n, 4, device=dev), torch.zeros(n, device=dev), torch.zeros(n, dtype=torch.int64, device=dev), 0.45)
+
+
 def test_batched_nms_takes_arbitrary_int64_category_ids(dev):
     """torchvision.ops.batched_nms accepts any int64 ids; the kernel's records hold 12 bits of class.  Ids >= 4096, negative ids and ids 2^40 apart must not alias:
     they are renumbered densely before the call, and more than 4096 distinct ids are refused"""
@@ -921,6 +950,103 @@ def test_postprocess_vs_oracle(dev):
             np.testing.assert_array_equal(d["labels"].cpu().numpy(), r["labels"].numpy())
             np.testing.assert_allclose(d["scores"].cpu().numpy(), r["scores"].numpy(), rtol=2e-6, atol=1e-7)
             np.testing.assert_allclose(d["boxes"].cpu().numpy(), r["boxes"].numpy(), rtol=1e-5, atol=1e-4)
+
+
+def _gpu_post(dev, heads, strides, anchors, nc, thr, k, cand_cap, fill):
+    """the post-process op on reference-layout head outputs under the host protocol of yolort_amd/ops.py::postprocess_logits, with the output arrays pre-filled with
+    `fill` -> PostBuffers of the last pass"""
+    from yolort_amd import _lib
+    from yolort_amd.engine import Plan, View
+    n, kk = heads[0].shape[0], nc + 5
+    inputs = []
+    for ho in heads:
+        cs = (3 * kk + 3) // 4 * 4
+        t = torch.zeros(n, ho.shape[2], ho.shape[3], cs, device=dev, dtype=torch.float32)
+        t[..., : 3 * kk] = ho.to(dev).permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * kk)
+        inputs.append(t)
+    cap, flags = cand_cap, 0
+    while True:
+        plan = Plan(dev, torch.float16)
+        views = [View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * kk, t.shape[3]) for t in inputs]
+        pb = plan.postprocess(views, strides, anchors, nc, thr, 0.45, k, cap, flags=flags)
+        pb.boxes.fill_(fill), pb.scores.fill_(fill), pb.labels.fill_(int(fill)), pb.status_count.fill_(int(fill))
+        plan.run()
+        st = pb.status.cpu().tolist()
+        if st[1] == 0:
+            return pb
+        if not st[1] & 1:
+            flags = _lib.POST_EXACT_FULL
+            continue
+        need = max(st[0], st[3] * n)
+        cap = max(int(need * 1.25) + 1024, 2 * cap)
+        cap = n * (1 << ((cap + n - 1) // n - 1).bit_length())
+
+
+def _assert_post_equals_oracle(pb, ref, fill):
+    """counts, labels, order exact; scores / boxes to the rounding of expf (the constants of test_postprocess_vs_oracle); nothing written past the counts"""
+    count, boxes, scores, labels = pb.count.cpu(), pb.boxes.cpu(), pb.scores.cpu(), pb.labels.cpu()
+    for i, r in enumerate(ref):
+        c = int(count[i])
+        assert c == len(r["scores"]), (i, c, len(r["scores"]))
+        np.testing.assert_array_equal(labels[i, :c].numpy(), r["labels"].numpy())
+        np.testing.assert_allclose(scores[i, :c].numpy(), r["scores"].numpy(), rtol=2e-6, atol=1e-7)
+        np.testing.assert_allclose(boxes[i, :c].numpy(), r["boxes"].numpy(), rtol=1e-5, atol=1e-4)
+        assert (scores[i, c:] == fill).all() and (labels[i, c:] == int(fill)).all() and (boxes[i, c:] == fill).all(), f"image {i}: slots past the count were written"
+
+
+@pytest.mark.parametrize("nc", _post_cases.POST_CLASS_COUNTS)
+def test_postprocess_vs_oracle_class_counts(dev, nc):
+    """test_postprocess_vs_oracle at the class counts where the decode changes shape: 1 (one label bit, the smallest legal count), 27 / 28 (both sides of an anchor
+    padding), 80 / 81 (255 channels = one float4 pass per pixel / the first count that needs two), 91, 124 (the first the fused head refuses), 166 (3 * 171 = 513
+    channels: the first pixel wider than the 512-record wave buffer), 200 and 601 (a pixel passes 600 / 1803 records: the buffer is flushed in the middle of a pixel).
+    Three images on levels (20, 24), (10, 12), (5, 6); per class count the runs of _post_cases.post_runs: the two settings of test_postprocess_vs_oracle, top-k cuts
+    at 1 / 7 / 300 with more survivors than that, a middle image without candidates, a batch without any (counts all 0).  Nothing is written past the counts."""
+    from oracle import yolov5_oracle as O
+    shapes = [(20, 24), (10, 12), (5, 6)]
+    strides, anchors = O.anchors_for(3)
+    refs = {}
+    for variant, thr, k, truncates in _post_cases.post_runs(nc, sum(3 * h * w for h, w in shapes)):
+        heads = _post_cases.post_heads(nc, shapes, empty=_post_cases.POST_EMPTY[variant])
+        if (variant, thr) not in refs:
+            pred = O.decode(heads, strides, anchors)
+            refs[variant, thr] = (pred, O.postprocess(pred, thr, 0.45, 1 << 30))   # the top-k cut is a slice of the un-truncated result (box_head.py:423)
+        pred, full = refs[variant, thr]
+        survivors, hot = _post_cases.assert_post_case_is_not_vacuous(nc, variant, thr, k, truncates, pred, shapes, full)
+        print(f"nc={nc} {variant} thr={thr} k={k}: candidates {_post_cases.oracle_candidates_per_anchor(pred, thr).sum(1).tolist()} survivors {survivors} hottest pixel {hot}")
+        pb = _gpu_post(dev, heads, strides, anchors, nc, thr, k, max(4096, 2048 * 3), -3.0)
+        _assert_post_equals_oracle(pb, [{key: v[:k] for key, v in r.items()} for r in full], -3.0)
+
+
+def test_postprocess_batch_size_limit(dev):
+    """1 025 images are refused by name when the op is added to a plan and by ymi_postprocess itself BEFORE anything is enqueued -- status words and outputs keep their
+    pattern -- and 1 024 images (one 2 x 2 level, two classes) equal the oracle"""
+    from oracle import yolov5_oracle as O
+    from yolort_amd import _lib
+    from yolort_amd._lib import YmiError
+    from yolort_amd.engine import Plan, View
+    strides, anchors = [8], [O.ANCHORS_P5[0]]
+    g = torch.Generator().manual_seed(1025)
+    n = 1025
+    t = torch.zeros(n, 1, 1, 24, device=dev)
+    t[..., :21] = (torch.randn(n, 1, 1, 21, generator=g) + 1.0).to(dev)
+    plan = Plan(dev, torch.float16)
+    view = View(t.view(-1), 0, n, 1, 1, 21, 24)
+    with pytest.raises(YmiError, match="1024"):
+        plan.postprocess([view], strides, anchors, 2, 0.3, 0.45, 10, n * 64)
+    pb, d = plan.post_desc([(1, 1)], n, strides, anchors, 2, 0.3, 0.45, 10, n * 64, logits=[view])
+    pb.boxes.fill_(-3.0), pb.scores.fill_(-3.0), pb.labels.fill_(-3), pb.status_count.fill_(-3)
+    rc = plan.lib.ymi_postprocess(C.byref(d), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc < 0
+    with pytest.raises(YmiError, match="1024"):
+        _lib.check(rc, "ymi_postprocess")
+    for name, v in (("boxes", pb.boxes), ("scores", pb.scores), ("labels", pb.labels), ("status / count", pb.status_count)):
+        assert bool((v == -3).all()), f"{name} was written although the batch was refused"
+    heads = [torch.randn(1024, 3, 2, 2, 7, generator=g) + 1.0]
+    ref = O.postprocess(O.decode(heads, strides, anchors), 0.3, 0.45, 10)
+    pb = _gpu_post(dev, heads, strides, anchors, 2, 0.3, 10, 1024 * 64, -3.0)
+    _assert_post_equals_oracle(pb, ref, -3.0)
+    assert int(pb.count.sum()) > 1024
 
 
 @pytest.mark.parametrize("aw,expect_short", [(30.0, False), (400.0, True)])

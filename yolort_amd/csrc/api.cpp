@@ -57,6 +57,7 @@ int stem_body1_desc_launch(const ymi_conv_desc* stem, const ymi_conv_desc* body1
 int postprocess_launch(const ymi_post_desc* d, hipStream_t s);
 int post_begin_launch(const ymi_post_desc* d, hipStream_t s);
 int post_finish_launch(const ymi_post_desc* d, hipStream_t s);
+int post_check_batch(const ymi_post_desc* d);
 int conv_head_decode_launch(const ymi_conv_desc* d, const ymi_post_desc* post, int level, hipStream_t s);
 int conv_head_decode_group_launch(const ymi_conv_desc* descs, int n_levels, const ymi_post_desc* post, hipStream_t s);
 
@@ -241,6 +242,7 @@ extern "C" int ymi_plan_add_act(ymi_plan* p, void* y, int y_cstride, int npix, i
 
 extern "C" int ymi_plan_add_postprocess(ymi_plan* p, const ymi_post_desc* d) {
     YMI_REQUIRE(p && d, "ymi_plan_add_postprocess: null argument");
+    if (const int rc = post_check_batch(d)) return rc;
     Op op;
     memset(&op, 0, sizeof(op));
     op.kind = OP_POST;
@@ -264,6 +266,7 @@ static int add_post_op(ymi_plan* p, OpKind kind, const ymi_post_desc* d, const y
 
 extern "C" int ymi_plan_add_post_begin(ymi_plan* p, const ymi_post_desc* d) {
     YMI_REQUIRE(p && d, "ymi_plan_add_post_begin: null argument");
+    if (const int rc = post_check_batch(d)) return rc;
     return add_post_op(p, OP_POST_BEGIN, d, nullptr, 0);
 }
 
@@ -287,6 +290,7 @@ extern "C" int ymi_plan_add_head_decode_group(ymi_plan* p, const ymi_conv_desc* 
 
 extern "C" int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d) {
     YMI_REQUIRE(p && d, "ymi_plan_add_post_finish: null argument");
+    if (const int rc = post_check_batch(d)) return rc;
     return add_post_op(p, OP_POST_FINISH, d, nullptr, 0);
 }
 

@@ -11,7 +11,9 @@
 // Record format (96 bits): hi = img << 32 | ~score_bits (u64), lo = cand = anchor << L | label (u32)
 // with L = label bits.  Sorting records ascending by (hi, lo) gives, per image, score descending
 // with ties in candidate order (anchor asc, class asc) == a stable descending sort of the
-// reference's torch.where order (box_head.py:418).
+// reference's torch.where order (box_head.py:418).  ~score_bits descends only for non-negative floats: that is the range of the in-plan producers
+// (decode_kernel, the head epilogue: sigmoid * sigmoid above a threshold), whose records are bit-inverted back into the score by the top-k gather.  The stand-alone
+// ymi_batched_nms takes ANY non-NaN float score (torchvision's contract) and builds its key with nms_score_key instead.
 #include "post_common.hpp"
 #include <cstdlib>
 
@@ -59,6 +61,10 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
 
     auto flush = [&]() {
         flush_records(k_, bhi, blo, fill, fill_img, lane);
+        // every lane has copied its share before the buffer is refilled: no instruction on the GPU (a wave's LDS accesses stay in order), a wave sync on the CPU
+        // simulator (tests/hipsim), whose lanes do not run in lockstep -- the flush in the MIDDLE of a pixel (more than DEC_BUF records: nc >= 171) is followed by
+        // the record writes without any shuffle in between, and its lane 0 overwrote records the other lanes had not copied yet (cf. head_decode.hpp)
+        __builtin_amdgcn_wave_barrier();
         fill = 0;
     };
 
@@ -833,7 +839,7 @@ __global__ __launch_bounds__(1024) void select_prefix_kernel(uint64_t* in_hi, ui
 constexpr int RANK_IT = 256;    // keys ranked per block
 constexpr int RANK_JT = 256;    // keys of a j-slice (4 KiB of LDS: G and P key of each)
 constexpr int RANK_GRID = 1024; // blocks of the ranking kernel (they walk the pair list of the whole batch)
-constexpr int RANK_NIMG = 1024; // images per batch the ranking kernel's per-block table holds (larger batches: the one-block-per-image sort)
+constexpr int RANK_NIMG = 1024; // images per batch the ranking kernel's per-block table holds; post_check_batch refuses a larger batch (there is no fallback)
 
 __device__ __forceinline__ uint64_t p_key_of(uint64_t g, int label_bits) {
     return ((g & ((1ull << label_bits) - 1ull)) << (64 - label_bits)) | (g >> label_bits);
@@ -1303,10 +1309,18 @@ static int sort_nms_gather(const Workspace& w, SortState st, int* status, int ca
     return nms_gather(w, g, phi, plo, status, cap, n_img, label_bits, total_anchors, nms_thresh, K, rescale, out_boxes, out_scores, out_labels, out_count, s, nullptr, out_slab);
 }
 
-static int post_validate(const ymi_post_desc* d, bool need_logits, PostLayout& L, Workspace& w) {
+// The batch size a descriptor may carry: the per-image path ranks the whole batch through one LDS table (rank_image_kernel), and include/yolort_amd.h gives that limit
+// for every path.  Checked when an op is added to a plan (api.cpp) and first thing in every stage, so a larger batch is refused before anything is enqueued.
+int post_check_batch(const ymi_post_desc* d) {
     YMI_REQUIRE(d != nullptr, "ymi_postprocess: null descriptor");
+    YMI_REQUIRE(d->n >= 1, "ymi_postprocess: batch size %d out of range", d->n);
+    YMI_REQUIRE(d->n <= RANK_NIMG, "ymi_postprocess: more than %d images in a batch (got %d); split the batch", RANK_NIMG, d->n);
+    return YMI_OK;
+}
+
+static int post_validate(const ymi_post_desc* d, bool need_logits, PostLayout& L, Workspace& w) {
+    if (const int rc = post_check_batch(d)) return rc;
     YMI_REQUIRE(d->num_levels >= 1 && d->num_levels <= YMI_MAX_LEVELS, "ymi_postprocess: num_levels %d out of range", d->num_levels);
-    YMI_REQUIRE(d->n >= 1 && d->n <= 65535, "ymi_postprocess: batch size %d out of range", d->n);
     YMI_REQUIRE(d->num_classes >= 1 && d->num_classes <= 4096, "ymi_postprocess: num_classes %d out of range", d->num_classes);
     YMI_REQUIRE(d->out_boxes && d->out_scores && d->out_labels && d->out_count && d->status && d->ws, "ymi_postprocess: null buffer");
     YMI_REQUIRE(d->detections_per_img >= 1 && d->cand_cap >= 1, "ymi_postprocess: detections_per_img and cand_cap must be positive");
@@ -1404,7 +1418,6 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
             hipLaunchKernelGGL(sel_copyback_kernel, dim3(cdiv(RANK_MAX, 256), d->n), dim3(256), 0, s, w.hi[0], w.lo[0], w.hi[1], w.lo[1], sel_state, w.sel_count, cap_img);
         }
         const int rank_cap = cap_img < RANK_MAX ? cap_img : RANK_MAX;   // no image holds more than cap_img records
-        YMI_REQUIRE(d->n <= RANK_NIMG, "ymi_postprocess: more than %d images in a batch", RANK_NIMG);
         hipLaunchKernelGGL(rank_image_kernel, dim3(RANK_GRID), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.sel_count, d->n, cap_img,
                            L.label_bits, rank_g, rank_p);
         hipLaunchKernelGGL(scatter_ranks_kernel, dim3(cdiv(rank_cap, RANK_IT), d->n), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, L.label_bits,
@@ -1440,13 +1453,22 @@ int postprocess_launch(const ymi_post_desc* d, hipStream_t s) {
 // ---- stand-alone batched NMS (one image) -------------------------------------------------
 constexpr int NMS_LABEL_BITS = 12;
 
+// Sort key of an arbitrary (non-NaN) float score, ascending key == descending score: the order-preserving map of IEEE floats to unsigned (all bits of a negative
+// value flipped, the sign bit of a non-negative one set), complemented.  -0.0 is +0.0 first: the two compare equal, so they must tie (and fall back to index order).
+__device__ __forceinline__ uint32_t nms_score_key(float score) {
+    uint32_t u = __float_as_uint(score);
+    if (u == 0x80000000u) u = 0u;
+    const uint32_t ascending = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~ascending;
+}
+
 __global__ __launch_bounds__(256) void nms_make_records_kernel(const float* boxes, const float* scores, const int* labels, int n, float* boxes_all,
                                                                uint64_t* hi, uint32_t* lo, int* status) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) { status[ST_NCAND] = n; status[ST_OVERFLOW] = 0; status[ST_NSEG] = 0; status[ST_RSV] = 0; }
     if (i >= n) return;
     *reinterpret_cast<f32x4*>(boxes_all + (int64_t)i * 4) = *reinterpret_cast<const f32x4*>(boxes + (int64_t)i * 4);
-    hi[i] = (uint64_t)(~__float_as_uint(scores[i]));
+    hi[i] = (uint64_t)nms_score_key(scores[i]);
     lo[i] = ((unsigned)i << NMS_LABEL_BITS) | ((unsigned)labels[i] & ((1u << NMS_LABEL_BITS) - 1u));
 }
 

@@ -15,7 +15,9 @@ from .engine import Plan, View
 def batched_nms(boxes: Tensor, scores: Tensor, labels: Tensor, iou_threshold: float) -> Tensor:
     """Class-aware NMS of one image on the MI355X; returns kept indices (int64) in score-descending
     stable order -- the contract of torchvision.ops.batched_nms as called at
-    yolort/models/box_head.py:422."""
+    yolort/models/box_head.py:422.  Scores may be any float values: negative ones, signed zeros
+    (-0.0 and +0.0 tie, the lower index first), infinities and subnormals are ordered as floats compare.  NaN scores and NaN
+    coordinates are outside the contract: what is returned for them is unspecified.  At most 2^20 - 1 boxes per call."""
     lib = _lib.load(require_gpu=True)
     if not boxes.is_cuda:
         raise YmiError("batched_nms runs on an MI355X only (no CPU fallback)")
