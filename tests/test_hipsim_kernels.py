@@ -1622,3 +1622,146 @@ def test_c3_strip_kernel_with_column_tiles(sim, case):
     side (recomputed); results bit-identical to the separate launches, like the full-width strips"""
     dtype, n, h, w, c_in, c_, nb, shortcut, blocks, geom = case
     _run_c3_tile_case(sim, dtype, n, h, w, c_in, c_, nb, shortcut, t3x3=91 if c_ == 128 else 92, blocks=blocks, geom=geom)
+
+
+# ---- per-element checks on exactly representable operands (tests/_exact.py): the CPU half of tests/test_conv_exact_gpu.py -------------------------------------------------
+import _exact  # noqa: E402
+
+# (the register-staged 16-bit kernel, tile 145 and the library rule are not part of the simulator build; every tile id runs on the GPU -- here the first and the last tile of
+# each family in fp16 and other tiles of the same families in bf16: a lane-accurate launch costs tenths of a second)
+_EXACT_SIM_FP16 = [12, 66, 111, 116, 31, 37, 91, 95, 121, 124, 141, 155, 131, 132, 133, 134, 135, 137, 138]
+_EXACT_SIM_BF16 = [21, 61, 113, 34, 93, 122, 143, 152, 131, 132, 133, 134, 135, 138]
+
+
+def _exact_sim_launch(sim, dtype, tile, case, act, residual):
+    """one launch on exact operands; returns the (n, ho, wo, cout) output, or None when the kernel refused the shape with YMI_EINVAL (and wrote nothing)"""
+    from yolort_amd import engine
+    from yolort_amd._lib import ACT_NONE, ACT_SILU
+    n, h, w, cin, cout, k, s = case
+    x, wt, bias, res = _exact.exact_operands(*case)
+    ho, wo = _exact.out_hw(h, w, k, s)
+    cpu = torch.device("cpu")
+    if dtype == torch.float32:
+        pc = engine.PackedConv(wt.float(), bias.float(), None, dtype, cpu, cin_pad=cin)
+        numel = n * h * w * cin
+        xt = torch.zeros(numel + 64)
+        xt[:numel].view(n, h, w, cin)[:] = x.permute(0, 2, 3, 1).float()
+        wide_t = torch.zeros(n, ho, wo, cout + 32)
+        rt = res.permute(0, 2, 3, 1).float().contiguous() if residual else None
+        d = _f32_desc((xt, n, h, w, cin, numel), pc, wide_t[..., 16:16 + cout], tile, k, s, k // 2, res=rt, act=ACT_SILU if act else ACT_NONE)
+        d.y_cstride = cout + 32
+        got_view = wide_t[..., 16:16 + cout]
+    else:
+        pc = engine.PackedConv(wt.float(), bias.float(), None, dtype, cpu)
+        xb = Buf(n, h, w, cin, dtype, fill=x.permute(0, 2, 3, 1))
+        wide = Buf(n, ho, wo, cout + 32, dtype)           # the output is a channel slice of a wider buffer
+        yv = wide.slice_c(16, cout)
+        rb = Buf(n, ho, wo, cout, dtype, fill=res.permute(0, 2, 3, 1)) if residual else None
+        d = _conv_desc(xb, pc, yv, tile, k=k, pad=k // 2, res=rb, stride=s)
+        d.act = ACT_SILU if act else ACT_NONE
+        if k > 1:
+            kt = pc.ktab(w, xb.cs)
+            d.ktab = kt.data_ptr()
+        wide_t, got_view = wide.view(), yv.view()
+    rc = sim.sim_conv2d(C.byref(d))
+    if rc != 0:
+        assert rc == -1, f"tile {tile} {case}: refusals carry YMI_EINVAL, got {rc}: {sim.sim_last_error().decode()}"
+        assert float(wide_t.float().abs().max()) == 0, f"tile {tile} {case}: refused, yet something was written"
+        return None
+    w_all = wide_t.float()
+    assert w_all[..., :16].abs().max().item() == 0 and w_all[..., 16 + cout:].abs().max().item() == 0, f"tile {tile} {case}: stray write outside the channel slice"
+    return got_view.clone()
+
+
+def _exact_sim_tile(sim, tile, dtype):
+    """_exact.sim_cases(tile) in both activation modes (the large map of the general families: one of the two per launch): act none bit-identical to the once-rounded float64 reference (shortcut on every other case); SiLU within 1 ulp (the
+    simulator's exp2f and 1/x are near-exact: off by one only next to a rounding tie) and |mean signed error| <= 0.1 ulp over the case"""
+    tally = {0: _exact.Tally(), 1: _exact.Tally()}
+    one_shape = _exact.family_of(tile) in ("c32", "res", "rw2", "rw3", "rs")
+    for i, case in enumerate(_exact.sim_cases(tile)):
+        # both modes on every small map; on the large map (the costly launches here: tenths of a second each) the general families take one mode, alternating from kind to kind and tile to tile
+        for act in (0, 1) if (one_shape or _exact.group_of(case) == "small maps") else ((i + tile) % 2,):
+            residual = (i // 2 + act) % 2 == 0 and not (act and tile in _exact.NO_SHORTCUT)
+            got = _exact_sim_launch(sim, dtype, tile, case, act, residual)
+            if got is None:
+                tally[act].refused += 1
+                continue
+            ref = _exact.reference64(*case, bool(act), residual)
+            label = f"tile {tile} {str(dtype)[6:]} {case} act={'silu' if act else 'none'} res={int(residual)}"
+            tally[act].add(*_exact.assert_elementwise(got, ref, dtype, 1 if act else 0, label), label, _exact.group_of(case))
+    for act in (0, 1):
+        assert tally[act].ran > 0 or (act == 0 and tile in _exact.SILU_ONLY), f"tile {tile}: every case was refused"
+        tally[act].verdict(f"sim tile {tile} {str(dtype)[6:]} act={'silu' if act else 'none'}")
+    return tally
+
+
+@pytest.mark.parametrize("tile", _EXACT_SIM_FP16)
+def test_exact_operands_per_element_fp16(sim, tile):
+    """every kernel family of the simulator build on exactly representable operands (tests/_exact.py: fp32 accumulation exact in any order), fp16 storage: 1x1 / 1xW / Hx1 maps,
+    maps smaller than the window, ragged maps, 3x3 at both strides, one tap per output channel -- per element against the float64 reference rounded once"""
+    _exact_sim_tile(sim, tile, torch.float16)
+
+
+@pytest.mark.parametrize("tile", _EXACT_SIM_BF16)
+def test_exact_operands_per_element_bf16(sim, tile):
+    """the same in bf16 storage (the 8-bit significand makes almost every output a rounding, ties included)"""
+    _exact_sim_tile(sim, tile, torch.bfloat16)
+
+
+@pytest.mark.parametrize("tile", [201, 206])
+def test_exact_operands_per_element_fp32(sim, tile):
+    """fp32 mode (csrc/conv_f32_pipe.hip): exact operands leave nothing to round without an activation -- bit-identical; SiLU (expf, true
+    division) within 1 ulp of fp32 of the float64 reference"""
+    tally = {0: _exact.Tally(), 1: _exact.Tally()}
+    for i, case in enumerate(_exact.cases(201, widths=[(32, 32), (48, 96)] if tile == 201 else [(64, 40)], shapes=_exact.SHAPES[:5])):
+        for act in ((i + tile) % 2,):
+            residual = (i // 2) % 2 == 0
+            got = _exact_sim_launch(sim, torch.float32, tile, case, act, residual)
+            assert got is not None, (tile, case)
+            label = f"fp32 tile {tile} {case} act={act} res={int(residual)}"
+            # SiLU + shortcut cancels, and the error of SiLU -- an ulp of ITS magnitude -- is many ulps of a small sum: the distance is measured at max(|SiLU|, |sum|), and the
+            # bound is 1 + 1 (SiLU's ulp, then the addition's own rounding against the reference's single one)
+            scale = _exact.reference64(*case, True, False) if (act and residual) else None
+            tally[act].add(*_exact.assert_elementwise(got, _exact.reference64(*case, bool(act), residual), torch.float32, (2 if scale is not None else 1) if act else 0, label, scale64=scale),
+                           label, _exact.group_of(case))
+    for act in (0, 1):
+        tally[act].verdict(f"sim fp32 tile {tile} act={act}")
+
+
+@pytest.mark.parametrize("tile", [153, 154])
+def test_exact_unknown_row_transposed_ids_are_refused(sim, tile):
+    """the 15x range has no variants 13 / 14: refused with YMI_EINVAL, nothing written"""
+    assert _exact_sim_launch(sim, torch.float16, tile, (2, 3, 3, 32, 32, 1, 1), 1, False) is None
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("act_name", ["hardswish", "leaky"])
+def test_exact_legacy_activation_domain(sim, act_name, dtype):
+    """ymi_act over the whole domain: every finite fp16 value / every finite bf16 value with |v| <= 2^17, and -inf -- class (NaN, +-0, +-inf) as torch's fp32 function stores it,
+    finite results within 1 ulp of the float64 function rounded once"""
+    from yolort_amd._lib import ACT_HARDSWISH, ACT_LEAKY, dtype_code
+    pre = torch.cat([_exact.act_domain(dtype), torch.full((32,), float("-inf"), dtype=dtype)])
+    buf = pre.clone().view(-1, 32)
+    _check(sim, sim.ymi_act(buf.data_ptr(), 32, buf.shape[0], 32, dtype_code(dtype), ACT_HARDSWISH if act_name == "hardswish" else ACT_LEAKY, None, 0, None))
+    worst, mean, cnt = _exact.assert_act_domain(buf.reshape(-1), pre.double(), act_name, dtype, 1, f"ymi_act {act_name} {dtype}")
+    print(f"EXACT sim ymi_act {act_name} {str(dtype)[6:]}: worst {worst:.3f} ulp, mean signed {mean:+.4f} ulp over {cnt} values")
+    assert abs(mean) <= 0.1
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_exact_silu_domain_through_a_pointwise_convolution(sim, dtype):
+    """every finite fp16 value (bf16: |v| <= 2^17) as the pre-activation of the shared 16-bit epilogue, through an identity 1x1 convolution (tile 121, one launch): both ends
+    of SiLU (exp2 overflowing to inf at v < -88.7: rcp(inf) = 0, the result is -0; underflowing at v > 88.7), subnormal results, +-0"""
+    from yolort_amd import engine
+    x, wt, bias, pre = _exact.silu_domain_problem(dtype)
+    npix = x.shape[0]
+    xb = Buf(1, 1, npix, 32, dtype, fill=x)
+    yb = Buf(1, 1, npix, 64, dtype)
+    pc = engine.PackedConv(wt.float().view(64, 32, 1, 1), bias.float(), None, dtype, torch.device("cpu"))
+    _check(sim, sim.sim_conv2d(C.byref(_conv_desc(xb, pc, yb, 121))))
+    got = yb.view().reshape(-1)
+    worst, mean, cnt = _exact.assert_act_domain(got, pre.reshape(-1), "silu", dtype, 1, f"silu domain {dtype}")
+    print(f"EXACT sim silu domain {str(dtype)[6:]}: worst {worst:.3f} ulp, mean signed {mean:+.4f} ulp over {cnt} values")
+    assert abs(mean) <= 0.1
+    if dtype == torch.float16:
+        assert int(((got.float().abs() > 0) & (got.float().abs() < 2.0 ** -14)).sum()) > 1000   # subnormal results are part of the domain

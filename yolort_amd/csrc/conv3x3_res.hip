@@ -162,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_res_kernel(const ConvArgs a, i
             if (has_res) unswap_residual_packet(rw[i][g >> 1], rv, g);
         }
         f32x2 v = {acc_prev[i][(g + h) * 4 + 2 * p], acc_prev[i][(g + h) * 4 + 2 * p + 1]};
-        v = silu_pair(v);
+        v = silu_pair<DT>(v);
         if (has_res) v = v + unpack16<DT>(rv[g + h][p]);
         pk[h][p] = cvt_pk16<DT>(v);
         if constexpr ((s & 3) == 3) {

@@ -64,7 +64,16 @@ __device__ __forceinline__ int fast_div(int n, int d, unsigned magic) {
     return q;
 }
 
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * v)); }
+// bf16 storage: for v in (-88.72, -87.34) the denominator 1 + exp(-v) lies in (2^126, 2^128) and its reciprocal is a SUBNORMAL fp32 number, which v_rcp_f32 flushes to
+// zero -- the result (about -5e-37, a normal bf16 number that torch's x / (1 + exp(-x)) keeps) came out as -0.  Numerator and denominator are therefore both scaled by
+// 1/4: (v/4) * rcp((1 + e)/4).  Scaling by a power of two is exact, so every other result keeps its bits, and inf / 0 / NaN keep their classes.  fp16 cannot hold such
+// values (they round to -0 either way): its epilogues are unchanged.
+template <int DT>
+__device__ __forceinline__ float silu(float v) {
+    const float e = __builtin_amdgcn_exp2f(-1.44269504088896341f * v);
+    if constexpr (DT == YMI_BF16) return (0.25f * v) * __builtin_amdgcn_rcpf(0.25f * e + 0.25f);
+    else return v * __builtin_amdgcn_rcpf(1.0f + e);
+}
 
 // compile-time loop: f(std::integral_constant<int, I>{}) for I = 0 .. N-1
 template <int I, int N, class F>
@@ -151,7 +160,7 @@ __device__ __forceinline__ void finish_subtile(const ConvArgs& a, const f32x16& 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             float t = acc[g * 4 + e];
-            if (a.act == YMI_ACT_SILU) t = silu(t);
+            if (a.act == YMI_ACT_SILU) t = silu<DT>(t);
             v[g][e] = t;
         }
         if constexpr (RES) {
@@ -256,11 +265,18 @@ __device__ __forceinline__ f32x2 unpack16(uint32_t u) {
 // fp32 instruction above two scalar ones when it sits beside MFMAs -- an A/B knob of the fused stem kernel's stage 1)
 // SiLU of two fp32 values with packed instructions: x * rcp(1 + exp2(-x * log2 e)) -- THE arithmetic of every 16-bit epilogue (one definition: kernels that
 // spread a tile's epilogue over the next tile's MFMAs, conv3x3_res.hip, must round exactly like the ones that run it in one piece)
+// (bf16: numerator and denominator scaled by 1/4, see silu<DT> above)
+template <int DT>
 __device__ __forceinline__ f32x2 silu_pair(f32x2 v) {
-    const f32x2 nl2e = {-1.44269504088896341f, -1.44269504088896341f}, one = {1.0f, 1.0f};
+    const f32x2 nl2e = {-1.44269504088896341f, -1.44269504088896341f}, one = {1.0f, 1.0f}, quarter = {0.25f, 0.25f};
     const f32x2 t = v * nl2e;
     f32x2 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    e = e + one;
+    if constexpr (DT == YMI_BF16) {
+        e = e * quarter + quarter;
+        v = v * quarter;
+    } else {
+        e = e + one;
+    }
     const f32x2 r = {__builtin_amdgcn_rcpf(e[0]), __builtin_amdgcn_rcpf(e[1])};
     return v * r;
 }
@@ -279,8 +295,15 @@ __device__ __forceinline__ void silu_pack_subtile(const f32x16& acc, const u32x2
                     float a0 = v[0], a1 = v[1];
                     float e0 = __builtin_amdgcn_exp2f(__fmul_rn(a0, -1.44269504088896341f)), e1 = __builtin_amdgcn_exp2f(__fmul_rn(a1, -1.44269504088896341f));
                     asm volatile("" : "+v"(e0), "+v"(e1));   // keep the two lanes of the pair apart (the SLP vectoriser would re-pack them)
-                    e0 = __fadd_rn(e0, 1.0f);
-                    e1 = __fadd_rn(e1, 1.0f);
+                    if constexpr (DT == YMI_BF16) {   // numerator and denominator scaled by 1/4, see silu<DT>
+                        e0 = __fadd_rn(__fmul_rn(e0, 0.25f), 0.25f);
+                        e1 = __fadd_rn(__fmul_rn(e1, 0.25f), 0.25f);
+                        a0 = __fmul_rn(a0, 0.25f);
+                        a1 = __fmul_rn(a1, 0.25f);
+                    } else {
+                        e0 = __fadd_rn(e0, 1.0f);
+                        e1 = __fadd_rn(e1, 1.0f);
+                    }
                     asm volatile("" : "+v"(e0), "+v"(e1));
                     const float r0 = __builtin_amdgcn_rcpf(e0), r1 = __builtin_amdgcn_rcpf(e1);
                     a0 = __fmul_rn(a0, r0);
@@ -289,7 +312,7 @@ __device__ __forceinline__ void silu_pack_subtile(const f32x16& acc, const u32x2
                     v[0] = a0;
                     v[1] = a1;
                 } else if constexpr (ACT) {
-                    v = silu_pair(v);
+                    v = silu_pair<DT>(v);
                 }
                 if constexpr (RES) v = v + unpack16<DT>(rv[g + h][p]);
                 pk[h][p] = cvt_pk16<DT>(v);

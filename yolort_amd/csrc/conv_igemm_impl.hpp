@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float t = acc[i][j][g * 4 + e] + b[e];
-                    if (a.act == YMI_ACT_SILU) t = silu(t);
+                    if (a.act == YMI_ACT_SILU) t = silu<DT>(t);
                     v[e] = t;
                 }
                 if (a.res != nullptr) {
