@@ -20,6 +20,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _head_cases
 import _post_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1152,6 +1153,52 @@ def test_fused_head_decode_equals_the_unfused_head(sim, dtype, nc):
         c = int(got["count"][i])
         assert c == len(r["scores"])
         np.testing.assert_array_equal(got["labels"][i, :c].numpy(), r["labels"].numpy())
+
+
+@pytest.mark.parametrize("name", list(_head_cases.SIM_SPECS))
+def test_fused_head_equals_the_oracle_on_exact_logits(sim, name):
+    """the simulator twin of tests/test_head_exact_gpu.py: conv_head_decode_group_kernel on inputs whose logits are exact (tests/_head_cases.py: one 1.0 per 32-channel block,
+    weights exact in fp16 and bf16) through post_begin / post_finish against O.postprocess(O.decode(logits)) -- counts, labels, order exact, scores / boxes to the rounding of
+    expf, nothing written past the counts.  sim-dense: a 32-pixel run across the image boundary passes more than HdCfg<1>::BUF = WL = 256 records per anchor (worklist spill,
+    record-buffer flush, image change inside an append); sim-tie-below-quarter: scores of exactly 0.5 and 0.25 against the float below 0.25 (the pre-filter's margin decides
+    the 0.25s); sim-thr-negative: every (anchor, class) pair passes, saturated logits included.  nms_thresh = 1.0 and k above the counts: the box of every candidate is
+    compared.  Passes under both lane orders (HIPSIM_REVERSE=1)."""
+    from yolort_amd._lib import ACT_NONE, ConvDesc, PostDesc, dtype_code
+    case, want = _head_cases.head_case(name), _head_cases.head_reference(name)
+    print(_head_cases.assert_head_case_is_not_vacuous(case, want))
+    cpu, dtype, n, k, fill = torch.device("cpu"), case["dtype"], case["n"], case["k"], -3.0
+    head = _head_cases.make_head(case)
+    shapes, nl = case["shapes"], len(case["shapes"])
+    xs = [Buf(n, h, w, c, dtype, fill=torch.from_numpy(x)) for x, c, (h, w) in zip(case["x"], case["chans"], shapes)]
+    total_anchors, cap = sum(3 * h * w for h, w in shapes), case["cand_cap"]
+    out = dict(boxes=torch.full((n, k, 4), fill), scores=torch.full((n, k), fill), labels=torch.full((n, k), int(fill), dtype=torch.int64),
+               count=torch.full((n,), int(fill), dtype=torch.int32), status=torch.full((8,), int(fill), dtype=torch.int32))
+    ws = torch.full((int(sim.ymi_postprocess_ws_bytes(n, total_anchors, cap)),), 0x7f, dtype=torch.uint8)   # a dirty workspace
+    d = PostDesc()
+    for i, (h, w) in enumerate(shapes):
+        d.lh[i], d.lw[i], d.stride[i] = h, w, float(case["strides"][i])
+        for j in range(6):
+            d.anchors[i][j] = float(case["anchors"][i][j])
+    d.num_levels, d.n, d.num_classes = nl, n, case["nc"]
+    d.score_thresh, d.nms_thresh, d.detections_per_img = case["thr"], case["nms"], k
+    d.out_boxes, d.out_scores, d.out_labels, d.out_count = out["boxes"].data_ptr(), out["scores"].data_ptr(), out["labels"].data_ptr(), out["count"].data_ptr()
+    d.status, d.ws, d.ws_bytes, d.cand_cap, d.flags = out["status"].data_ptr(), ws.data_ptr(), ws.numel(), cap, 1   # exact full pass: no score prefix
+    arr, keep = (ConvDesc * nl)(), []
+    for i, xb in enumerate(xs):
+        pc = head.packed_anchor_major(i, dtype, cpu, case["chans"][i])
+        keep.append(pc)
+        cd = _conv_desc(xb, pc, xb, 0)
+        cd.y, cd.y_cstride, cd.act, cd.out_dtype = None, 0, ACT_NONE, dtype_code(torch.float32)
+        C.memmove(C.byref(arr, i * C.sizeof(ConvDesc)), C.byref(cd), C.sizeof(ConvDesc))
+    _check(sim, sim.ymi_post_begin(C.byref(d), None))
+    _check(sim, sim.sim_conv_head_decode_group(arr, nl, C.byref(d)))
+    _check(sim, sim.ymi_post_finish(C.byref(d), None))
+    st = out["status"].tolist()
+    assert st[1] == 0 and st[0] == int(case["cand"].sum()), st
+    _assert_post_equals_oracle(out, want, k, fill)
+    if case["expect_candidates"] is not None:
+        assert int(out["count"].sum()) == case["expect_candidates"]
+        assert all(torch.isin(out["scores"][i, : int(out["count"][i])], torch.tensor([0.25, 0.5, 1.0])).all() for i in range(n))
 
 
 @pytest.mark.parametrize("cout,hw", [(32, (64, 96)), (48, (40, 64)), (16, (32, 64))])

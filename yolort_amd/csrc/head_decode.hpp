@@ -143,11 +143,12 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
         const float o = sigmoid_acc(lobj);
         const bool pass = m_ok && o > k_.thr;      // score = cls * obj <= obj
         if (__ballot(pass) == 0) return;            // wave-uniform: nothing to find for this anchor
-        // cls * o > thr  =>  sigmoid(v) > thr / o  =>  v > logit(thr / o); the margin keeps the filter a superset
+        // cls * o > thr  =>  sigmoid(v) > thr / o  =>  v > logit(thr / o); the margin keeps the filter a superset.
+        // thr <= 0: every sigmoid exceeds thr / o <= 0, nothing may be filtered (the log of a negative p would be NaN and v > NaN false for every class)
         float theta = INFINITY;
         if (pass) {
             const float p = k_.thr / o;
-            theta = __logf(p / (1.0f - p)) - 0.02f;
+            theta = p > 0.0f ? __logf(p / (1.0f - p)) - 0.02f : -INFINITY;
         }
         const unsigned lo_base = (unsigned)anchor << k_.label_bits;
         static_for<0, TNA * 16>([&](auto rt) {
