@@ -1812,3 +1812,213 @@ def test_exact_silu_domain_through_a_pointwise_convolution(sim, dtype):
     assert abs(mean) <= 0.1
     if dtype == torch.float16:
         assert int(((got.float().abs() > 0) & (got.float().abs() < 2.0 ** -14)).sum()) > 1000   # subnormal results are part of the domain
+
+
+# ---- the first layer on exact operands (tests/_stem_cases.py): the CPU half of tests/test_stem_exact_gpu.py ----------------------------------------------------------------
+import _stem_cases as _stem  # noqa: E402
+
+_STEM_SIM_SHAPES = _stem.SHAPES[:6]          # up to (3, 18, 72); fp16 adds one of the two larger maps
+# (dtype, tile, shape, cout, weight set): the stem kernel (tile 41; the planar kernel runs the planar-capable ones of these too) at every cout on every shape, and generic
+# tiles of the simulator build on the im2col-table form at one cout per shape (the 8-wave and row-transposed tiles need cin % 32 == 0 and refuse the form: the GPU half
+# asserts that refusal for every id); ONE weight set per (shape, cout), rotating
+_STEM_SIM = []
+for _dt, _tiles, _shapes, _k in ((torch.float16, [41, 12, 24], _STEM_SIM_SHAPES + [_stem.SHAPES[6]], 0), (torch.bfloat16, [41, 21, 27], _STEM_SIM_SHAPES, 7)):
+    for _j, _tile in enumerate(_tiles):
+        for _i, _shape in enumerate(_shapes):
+            for _c, _cout in enumerate(_stem.COUTS):
+                if _tile == 41 or (_i + _j) % 4 == _c:
+                    _STEM_SIM.append((_dt, _tile, _shape, _cout, (_i + _j + _k) % _stem.SETS[_cout]))
+for _cout in _stem.COUTS:   # the single-tap channels of the stem-kernel launches reach all 108 taps at every cout
+    assert _stem.tap_cover([(c, s) for (_, t, _, c, s) in _STEM_SIM if c == _cout and t == 41]) == set(range(_stem.NTAPS)), _cout
+
+
+def _stem_sim_desc(cv, pc, og, act, tile, dtype):
+    """the stem's descriptor in its super-pixel form over a guarded canvas `cv` and output `og` (tests/_stem_cases.py Guard)"""
+    from yolort_amd._lib import ACT_NONE, ACT_SILU, ConvDesc, dtype_code
+    d = ConvDesc()
+    d.x, d.w, d.bias, d.y = cv.ptr, pc.w.data_ptr(), pc.bias.data_ptr(), og.ptr
+    d.n, d.h, d.w_in, d.cin, d.x_cstride = cv.n, cv.h, cv.w // 2, 8, 8
+    d.ho, d.wo, d.cout, d.cout_pad, d.y_cstride = og.h, og.w, pc.cout, pc.cout_pad, og.cs
+    d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, d.k_pad = 6, 3, 2, 1, 2, 1, pc.k_pad
+    d.act, d.dtype, d.out_dtype, d.tile = ACT_SILU if act else ACT_NONE, dtype_code(dtype), dtype_code(og.t.dtype), tile
+    d.zeros = cv.zeros
+    kt = pc.ktab(cv.w // 2, 8)
+    d.ktab = kt.data_ptr()
+    d._keep = kt
+    return d
+
+
+def _stem_sim_out(n, ho, wo, cout, dtype, dense=False):
+    cpu = torch.device("cpu")
+    if dense:
+        return _stem.Guard(n, ho, wo, cout, dtype, cpu).snapshot()
+    return _stem.Guard(n, ho, wo, cout, dtype, cpu, c0=16, cs=(cout + 7) // 8 * 8 + 32).snapshot()
+
+
+def _stem_sim_launch(sim, dtype, tile, x, pc, act, planar=False, out_dtype=None):
+    """one stem launch from the guarded canvas (sim_conv2d) or the guarded planar images (sim_conv_stem_planar; the canvas is then all NaN) -> output or None (refused, nothing written)"""
+    cpu = torch.device("cpu")
+    n, _, h, w = x.shape
+    ho, wo = _stem.stem_hw(h, w)
+    og = _stem_sim_out(n, ho, wo, pc.cout, out_dtype or dtype)
+    label = f"stem {'planar' if planar else 'canvas'} tile {tile} {dtype} {(n, h, w)} cout {pc.cout}"
+    if planar:
+        cv = _stem.Guard(n, h, w, 4, dtype, cpu).snapshot()
+        imgs, store = _stem.planar_images(x, dtype, cpu)
+        before = store.clone()
+        rc = sim.sim_conv_stem_planar(C.byref(_stem_sim_desc(cv, pc, og, act, 41, dtype)), (C.c_void_p * n)(*[im.data_ptr() for im in imgs]), n)
+        assert torch.equal(_stem.bits(store), _stem.bits(before))
+    else:
+        cv = _stem.canvas(x, dtype, cpu)
+        rc = sim.sim_conv2d(C.byref(_stem_sim_desc(cv, pc, og, act, tile, dtype)))
+    cv.assert_untouched(label)
+    if rc != 0:
+        assert rc == -1, f"{label}: refusals carry YMI_EINVAL, got {rc}: {sim.sim_last_error().decode()}"
+        og.assert_untouched(label + " (refused)")
+        return None
+    og.assert_only_the_view_written(label)
+    return og.view().clone()
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_exact_stem_per_element(sim, dtype):
+    """conv_stem_kernel (tile 41), conv_stem_planar_kernel and generic tiles on the stem's im2col form, on exact operands inside NaN guard bands: no activation bit-identical to
+    the once-rounded float64 reference (16-bit and, for the stem kernels, fp32 output), SiLU within 1 ulp and |mean| <= 0.1 ulp; planar == canvas bit for bit; W % 8 != 0 is
+    refused by the planar entry point; tile 41 must never refuse"""
+    from yolort_amd import engine
+    cpu = torch.device("cpu")
+    tally = {0: _exact.Tally(), 1: _exact.Tally(), "f32": _exact.Tally()}
+    ran, refused = {}, {}
+    for (dt, tile, shape, cout, seed) in _STEM_SIM:
+        if dt != dtype:
+            continue
+        x, wt, bias = _stem.stem_operands(*shape, cout, seed)
+        pc = engine.PackedConv(wt.float(), bias.float(), None, dtype, cpu, stem_superpixel=True)
+        small = _stem.group_of(shape) == "small maps"
+        modes = ((0, 1, "f32") if tile == 41 else (0, 1)) if small else ((seed + cout // 16) % 2,)
+        for mode in modes:
+            act, odt = mode == 1, (torch.float32 if mode == "f32" else dtype)
+            label = f"sim stem tile {tile} {dtype} {shape} cout {cout} set {seed} mode {mode}"
+            got = _stem_sim_launch(sim, dtype, tile, x, pc, act, out_dtype=odt)
+            if got is None:
+                assert tile != 41, label
+                tally[mode].refused += 1
+                refused.setdefault(tile, []).append((shape, cout))
+                continue
+            ran[tile] = ran.get(tile, 0) + 1
+            tally[mode].check(got, _stem.stem_reference64(*shape, cout, seed, act), odt, 1 if act else 0, label, group=_stem.group_of(shape))
+            if tile == 41:
+                twin = _stem_sim_launch(sim, dtype, 41, x, pc, act, planar=True, out_dtype=odt)
+                if _stem.planar_ok(shape):
+                    assert twin is not None and torch.equal(_stem.bits(twin), _stem.bits(got)), f"{label}: the planar form differs from the canvas form"
+                else:
+                    assert twin is None, f"{label}: the planar entry point took W % 8 != 0"
+    print(f"STEM sim {dtype}: launches that ran per tile {ran}; refused {refused}")
+    assert all(ran.get(t, 0) > 0 for (dt, t, _, _, _) in _STEM_SIM if dt == dtype), "a tile of the list refused every case"
+    for mode in tally:
+        tally[mode].verdict(f"sim stem {dtype} mode {mode}")
+
+
+def _exact_focus(version, cout, wt, bias):
+    from yolort_amd.v5.models.common import Focus
+    m = Focus(3, cout, k=3, version=version).eval()
+    bn = m.conv.bn
+    with torch.no_grad():
+        m.conv.conv.weight.copy_(wt.float())
+        bn.weight.copy_(torch.sqrt(bn.running_var.detach().to(torch.float32) + float(bn.eps)))   # as PackedConv computes it: scale = gamma / gamma = 1.0
+        bn.running_mean.zero_()
+        bn.bias.copy_(bias.float())
+    return m
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("version", ["r4.0", "r3.1"])
+def test_exact_focus_against_the_reference_formulation(sim, version, dtype):
+    """Focus(3, 32, k=3) through Focus.packed() (stem_weight's rearrangement, the exact BatchNorm fold) and the stem kernel, against Conv(12, 32, 3, 1, 1) over
+    focus_transform(x) in float64 -- the reference formulation: no activation bit-identical; SiLU (r4.0) 1 ulp; Hardswish (r3.1, its own ymi_act launch) 1 ulp"""
+    from yolort_amd._lib import ACT_HARDSWISH, dtype_code
+    cpu, cout = torch.device("cpu"), 32
+    tally = {"none": _exact.Tally(), "act": _exact.Tally()}
+    shapes = [s for s in _STEM_SIM_SHAPES if s[1] % 2 == 0]
+    for i, shape in enumerate(shapes):
+        seed = i % _stem.SETS[cout]
+        x, wt, bias = _stem.focus_operands(*shape, cout, seed)
+        pre = _stem.focus_pre64(*shape, cout, seed)
+        pc = _exact_focus(version, cout, wt, bias).packed(dtype, cpu)
+        w6 = pc.w[:cout, :144].float().view(cout, 6, 3, 2, 4)
+        assert float(w6[..., 3].abs().max()) == 0 and torch.equal(pc.bias[:cout].double(), bias)
+        assert torch.equal(F.conv2d(x, w6[..., :3].reshape(cout, 6, 6, 3).permute(0, 3, 1, 2).double(), bias, 2, 2), pre), "the packed weights do not carry the intended bits"
+        p = pre.permute(0, 2, 3, 1).contiguous()
+        for which in ("none", "act"):
+            label = f"sim focus {version} {dtype} {shape} set {seed} {which}"
+            got = _stem_sim_launch(sim, dtype, 41, x, pc, which == "act" and version == "r4.0")
+            assert got is not None, label
+            if which == "none":
+                ref = p
+            elif version == "r4.0":
+                ref = _exact.silu64(p)
+            else:
+                buf = got.contiguous()
+                _check(sim, sim.ymi_act(buf.data_ptr(), cout, buf.numel() // cout, cout, dtype_code(dtype), ACT_HARDSWISH, None, 0, None))
+                got, ref = buf, _exact.ACT_REFS["hardswish"][0](_exact.round_once(p, dtype).double())
+            tally[which].check(got, ref, dtype, 0 if which == "none" else 1, label, group=_stem.group_of(shape))
+    assert _stem.tap_cover([(cout, i % _stem.SETS[cout]) for i in range(len(shapes))]) == set(range(_stem.NTAPS))
+    for which in tally:
+        tally[which].verdict(f"sim focus {version} {dtype} {which}")
+
+
+def _stem_sim_fused(sim, dtype, x, w0, b0, w1, b1, form, label):
+    """body.1's output of the ONE launch (planar images / canvas) and of the two launches (the form's stem kernel, then tile 131), guard bands asserted -> (fused, separate)"""
+    from yolort_amd import engine
+    cpu = torch.device("cpu")
+    n, _, h, w = x.shape
+    hs, ws = _stem.stem_hw(h, w)
+    ho, wo = _stem.body1_hw(hs, ws)
+    pc0 = engine.PackedConv(w0.float(), b0.float(), None, dtype, cpu, stem_superpixel=True)
+    pc1 = engine.PackedConv(w1.float(), b1.float(), None, dtype, cpu)
+    kt = pc1.ktab(ws, 32)
+    outs = {}
+    for fused in (False, True):
+        cv = _stem.canvas(x, dtype, cpu) if form == "canvas" else _stem.Guard(n, h, w, 4, dtype, cpu).snapshot()
+        sg, og = _stem_sim_out(n, hs, ws, 32, dtype, dense=True), _stem_sim_out(n, ho, wo, 64, dtype)
+        d0 = _stem_sim_desc(cv, pc0, sg, True, 41, dtype)
+        d1 = _conv_desc(sg, pc1, og, 131, k=3, pad=1, stride=2)
+        d1.ktab = kt.data_ptr()
+        imgs, store = _stem.planar_images(x, dtype, cpu) if form == "planar" else ([], None)
+        ptrs = (C.c_void_p * n)(*[im.data_ptr() for im in imgs]) if form == "planar" else None
+        if fused:
+            _check(sim, sim.sim_stem_body1_planar(C.byref(d0), C.byref(d1), ptrs, n) if form == "planar" else sim.sim_stem_body1(C.byref(d0), C.byref(d1)))
+            sg.assert_untouched(f"{label}: the stem's output buffer")
+        else:
+            _check(sim, sim.sim_conv_stem_planar(C.byref(d0), ptrs, n) if form == "planar" else sim.sim_conv2d(C.byref(d0)))
+            sg.assert_only_the_view_written(f"{label}: the stem's output")
+            _check(sim, sim.sim_conv2d(C.byref(d1)))
+        og.assert_only_the_view_written(f"{label} fused={fused}")
+        cv.assert_untouched(label)
+        outs[fused] = og.view().clone()
+    return outs[True], outs[False]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("form", ["planar", "canvas"])
+def test_exact_fused_stem_body1(sim, form, dtype):
+    """stem + body.1 as one launch on exact operands, both input forms: bit-identical to the two launches (stem's output buffer untouched, NaN guard bands intact), and -- on
+    the problem whose intermediate is exact (stem pre-activations are integers in [19, 61]; body.1 pads with 0, not 40) -- within 1 ulp of the independent float64 two-layer
+    reference, |mean| <= 0.1 ulp, for the one launch and for the two"""
+    w1, b1 = _stem.body1_weights()
+    tally = {"fused": _exact.Tally(), "two launches": _exact.Tally()}
+    shapes = _STEM_SIM_SHAPES + ([_stem.SHAPES[7]] if dtype == torch.float16 else [])
+    for i, shape in enumerate(s for s in shapes if form == "canvas" or _stem.planar_ok(s)):
+        seed = i % _stem.SETS[32]
+        x, wt, bias = _stem.stem_operands(*shape, 32, seed)
+        label = f"sim fused {form} {dtype} {shape} set {seed}"
+        one, two = _stem_sim_fused(sim, dtype, x, wt, bias, w1, b1, form, label)
+        assert torch.equal(_stem.bits(one), _stem.bits(two)), f"{label}: differs from the two launches"
+        x, w0, b0, w1x, b1x = _stem.two_layer_operands(*shape)
+        label = f"sim two-layer {form} {dtype} {shape}"
+        one, two = _stem_sim_fused(sim, dtype, x, w0, b0, w1x, b1x, form, label)
+        ref = _stem.two_layer_reference64(*shape)
+        tally["fused"].check(one, ref, dtype, 1, label + " fused", group=_stem.group_of(shape))
+        tally["two launches"].check(two, ref, dtype, 1, label + " two launches", group=_stem.group_of(shape))
+    for k in tally:
+        tally[k].verdict(f"sim fused stem + body.1 {form} {dtype} {k}")

@@ -14,7 +14,7 @@
 //   stage 2  the 3x3 stride-2 convolution from that patch, folded weights resident in LDS in fragment order, one 32-pixel x
 //            32-cout tile per wave, the shared epilogue.
 // Both weight matrices are loaded once per block (the stem's 9 KiB into registers, body.1's 36 KiB into LDS); the planar patch of tile i+1 is DMA'd while stage 2 of tile i runs.
-// Results are BIT-IDENTICAL to the two separate launches (tests/test_hipsim_kernels.py on the CPU simulator, tests/test_ops_gpu.py).
+// Results are BIT-IDENTICAL to the two separate launches (tests/test_hipsim_kernels.py on the CPU simulator; tests/test_stem_exact_gpu.py::test_fused_stem_body1_exact on the GPU).
 #include "conv_common.hpp"
 
 namespace ymi {
