@@ -280,6 +280,15 @@ typedef struct ymi_post_desc {
  * truncated image ends with fewer kept boxes, bit 1 of status[1] is set and the caller re-runs the batch with
  * YMI_POST_EXACT_FULL (the Python host does this transparently). */
 #define YMI_POST_EXACT_FULL 1
+/* Best-class mode: ONE label per anchor -- the contract of ultralytics' non_max_suppression(..., multi_label=False) (yolort/v5/utils/general.py:572-583, what AutoShape
+ * uses) instead of yolort's multi-label PostProcess.  Per anchor: s_c = cls_c * obj (the very fp32 product of the default mode), conf = max_c s_c, label = the lowest
+ * class index with s_c == conf (torch.max(1)); the anchor is a candidate iff conf > score_thresh (strict), so there are at most total_anchors records per image and
+ * status[4] counts passing ANCHORS.  Sort (ties by anchor index), class-aware NMS, top-k, rescale, slab and status words are those of the default mode; with
+ * num_classes == 1 the two modes are bit-identical; thresholds <= 0 keep their meaning (every anchor yields its best class).  Honoured by ymi_postprocess,
+ * ymi_conv_head_decode, ymi_conv_head_decode_group, their ymi_plan_add_* forms and the replay of an exported plan (the descriptor travels with the plan).
+ * Differences from ultralytics: the NMS is the true class-aware NMS of this library, not the 4096-pixel class offset; there is no max_nms = 30000 cut of the
+ * candidates; scores stay fp32; `classes=` filtering and `agnostic=` are not provided. */
+#define YMI_POST_BEST_CLASS 2
 #define YMI_STATUS_OVERFLOW_CAPACITY 1 /* status[1] bit 0: candidate capacity exceeded (grow cand_cap) */
 #define YMI_STATUS_PREFIX_SHORT 2      /* status[1] bit 1: prefix too short, re-run with YMI_POST_EXACT_FULL */
 

@@ -63,6 +63,7 @@ REGION_CONST, REGION_SCRATCH, REGION_IO = 1, 2, 3
 TAG_NONE, TAG_INPUT, TAG_RESCALE, TAG_BOXES, TAG_SCORES, TAG_LABELS, TAG_STATUS_COUNT, TAG_SLAB = range(8)
 ABI_VERSION = 6   # include/yolort_amd.h YMI_ABI_VERSION
 POST_EXACT_FULL = 1
+POST_BEST_CLASS = 2   # YMI_POST_BEST_CLASS: one label per anchor (ultralytics' multi_label=False)
 
 
 class PostDesc(C.Structure):

@@ -14,6 +14,8 @@
 //   * drains the worklist 64 entries at a time (every lane busy): exact score as in the unfused kernel
 //     (sigmoid_acc, rounded product, strict >), records appended to a per-wave LDS buffer flushed with one atomic.
 //     (The LDS operand ring is dead by then and is reused for both.)
+// In best-class mode (YMI_POST_BEST_CLASS, CandSink::best) the last two steps become: in-register maximum of the anchor's class logits, exact scores of the classes near
+// it, one cross-half exchange, ONE record per passing (pixel, anchor) -- see the branch below.
 // Records and boxes are bit-identical to decode_kernel's (postprocess.hip), so sort / NMS / top-k are unchanged.
 #pragma once
 #include "conv_common.hpp"
@@ -143,6 +145,49 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
         const float o = sigmoid_acc(lobj);
         const bool pass = m_ok && o > k_.thr;      // score = cls * obj <= obj
         if (__ballot(pass) == 0) return;            // wave-uniform: nothing to find for this anchor
+        const unsigned lo_base = (unsigned)anchor << k_.label_bits;
+        if (k_.best) {
+            // Best-class mode (YMI_POST_BEST_CLASS; wave-uniform branch, the multi-label path below is untouched): ONE record per passing (pixel, anchor), the class
+            // with the largest PRODUCT, the lowest index among equal products.  Lanes l and l + 32 hold the pixel's logits in compile-time-indexed registers:
+            //   1. in-register maximum of the class LOGITS (rows c < 5 -- box, objectness -- and the padding rows c >= K, logit 0, are left out), one cross-half exchange;
+            //   2. exact scores -- the multi-label expression, bit for bit -- only of the classes at or above best_class_cut (post_common.hpp: a superset of the
+            //      classes that can reach or tie the largest product; it states what it assumes of sigmoid_acc), few per pixel, skipped row-wise by ballot;
+            //      a lane meets its rows in ascending class order, so a strict > keeps its lowest index;
+            //   3. one cross-half exchange of (score, class) under the total order (score descending, class ascending); the hi = 0 lane appends the record.
+            // register r of this lane is row c = cb + 4 * hi, cb = s * 32 + g * 8 + e a compile-time constant: a class row iff 5 <= c < K, i.e. cb < kcap (and, in the
+            // first group only, past the objectness row)
+            int kcap = h.K - 4 * hi;
+            float vmax = -INFINITY;
+            static_for<0, TNA * 16>([&](auto rt) {
+                constexpr int r = decltype(rt)::value;
+                constexpr int s = r / 16, g = (r % 16) / 4, e = r % 4, cb = s * 32 + g * 8 + e;
+                const float v = acc[q * TNA + s][0][g * 4 + e];
+                const bool cls = (cb >= 5 || (hi && cb >= 1)) && cb < kcap;
+                vmax = fmaxf(vmax, cls ? v : -INFINITY);
+            });
+            vmax = fmaxf(vmax, __shfl_xor(vmax, 32, 64));
+            // The second pass states its row tests on an opaque copy of kcap: left to itself the compiler keeps the 16 * TNA lane masks of the first pass alive for the
+            // second one (96 SGPRs at TNA = 3), runs out of scalar registers and spills them into VGPRs -- of the WHOLE kernel, the multi-label path included
+            // (90 -> 112 VGPRs and 5 -> 4 waves per SIMD at TNA = 3: profiles/best_class_head_registers.txt)
+            asm volatile("" : "+v"(kcap));
+            const float cut = best_class_cut(vmax, o);
+            BestClass b = best_none();
+            static_for<0, TNA * 16>([&](auto rt) {
+                constexpr int r = decltype(rt)::value;
+                constexpr int s = r / 16, g = (r % 16) / 4, e = r % 4, cb = s * 32 + g * 8 + e;
+                const float v = acc[q * TNA + s][0][g * 4 + e];
+                const bool pre = pass && (cb >= 5 || (hi && cb >= 1)) && (cb < kcap) && (v >= cut);
+                if (__ballot(pre) == 0) return;          // the common case
+                if (pre) {
+                    const float sc = __fmul_rn(sigmoid_acc(v), o);   // box_head.py:357 scores = cls * obj
+                    if (sc > b.s) b = BestClass{sc, cb + 4 * hi};
+                }
+            });
+            const BestClass t = {__shfl_xor(b.s, 32, 64), __shfl_xor(b.c, 32, 64)};
+            if (best_before(t.s, t.c, b)) b = t;
+            append(pass && hi == 0 && b.c != 0x7fffffff && b.s > k_.thr, b.s, lo_base | (unsigned)(b.c - 5), img);   // conf > thr, strict (general.py:583)
+            return;
+        }
         // cls * o > thr  =>  sigmoid(v) > thr / o  =>  v > logit(thr / o); the margin keeps the filter a superset.
         // thr <= 0: every sigmoid exceeds thr / o <= 0, nothing may be filtered (the log of a negative p would be NaN and v > NaN false for every class)
         float theta = INFINITY;
@@ -150,7 +195,6 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
             const float p = k_.thr / o;
             theta = p > 0.0f ? __logf(p / (1.0f - p)) - 0.02f : -INFINITY;
         }
-        const unsigned lo_base = (unsigned)anchor << k_.label_bits;
         static_for<0, TNA * 16>([&](auto rt) {
             constexpr int r = decltype(rt)::value;
             constexpr int s = r / 16, g = (r % 16) / 4, e = r % 4;

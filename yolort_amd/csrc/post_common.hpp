@@ -70,6 +70,7 @@ struct CandSink {
     int total_anchors;     // anchors per image over all levels
     int label_bits;
     float thr;             // score threshold (strict >)
+    int best;              // YMI_POST_BEST_CLASS: one record per anchor (its best class) instead of one per (anchor, class) pair; wave-uniform
 };
 
 // layout decisions shared by every producer / consumer of the records of one ymi_post_desc
@@ -94,10 +95,39 @@ inline CandSink make_sink(const ymi_post_desc* d, const Workspace& w, const Post
     k.boxes_all = w.boxes_all; k.hi = w.hi[0]; k.lo = w.lo[0]; k.status = d->status; k.cap = d->cand_cap;
     k.img_count = L.per_image ? w.img_count : nullptr; k.cap_img = L.cap_img;
     k.total_anchors = L.total_anchors; k.label_bits = L.label_bits; k.thr = d->score_thresh;
+    k.best = (d->flags & YMI_POST_BEST_CLASS) != 0;
     return k;
 }
 
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+// ---- best-class mode (YMI_POST_BEST_CLASS; ultralytics' non_max_suppression(..., multi_label=False), yolort/v5/utils/general.py:572-583) ----
+// An anchor yields at most ONE record: conf = max_c s_c over its classes, s_c = fmul_rn(sigmoid_acc(cls_c), obj) exactly as in multi-label mode, label = the LOWEST class
+// with s_c == conf (torch.max(1)'s first maximal index), candidate iff conf > thr (strict).  The running (score, class) pair of both producers:
+struct BestClass {
+    float s;   // best score so far; scores are >= 0, so -1 = none yet (a NaN score never enters)
+    int c;     // its class (channel) index; INT_MAX = none
+};
+__device__ __forceinline__ BestClass best_none() { return BestClass{-1.0f, 0x7fffffff}; }
+__device__ __forceinline__ bool best_before(float s, int c, const BestClass& b) { return s > b.s || (s == b.s && c < b.c); }
+
+// The fused head does not evaluate the exact score of every class: it takes the largest class LOGIT of the anchor first (vmax) and evaluates only the classes whose logit
+// is >= best_class_cut(vmax, obj).  The label rule is on the rounded PRODUCTS, and distinct logits give equal products (rounding; certainly where sigmoid_acc saturates at
+// 1.0 or flushes to 0), so the cut has to keep every class that can reach OR TIE the largest product.  It relies on two properties of f = sigmoid_acc, which is not assumed
+// monotone; tests/test_best_class.py sweeps them on the CPU over every fp32 logit in [-128, 32] and samples of every binade beyond:
+//   (A1) f never falls by more than 2^-21 (relative) on the way up:   x <= y                       =>  f(x) <= f(y) * (1 + 2^-21)
+//   (A2) a step of BEST_DELTA below a logit in [BEST_VLOW, BEST_VCAP] costs 2^-19:  x < fl(y - BEST_DELTA)  =>  f(x) <= f(y) * (1 - 2^-19)
+//        (d ln f / dv = 1 - f >= 1 / (1 + e^8) there: the true step is >= 2^-17.5; above BEST_VCAP the sigmoid flattens out -- it is exactly 1.0 from 17.4 on -- and no
+//        finite step would do, which is why the cut never rises above BEST_VCAP - BEST_DELTA: every class of the flat part is evaluated exactly)
+// With vcap = min(vmax, BEST_VCAP): a class below the cut has f(v) <= f(vcap) (1 - 2^-19) <= f(vmax) (1 + 2^-21) (1 - 2^-19) < f(vmax) (1 - 2^-20); both products are
+// rounded once (2^-24 relative) and the larger one is a normal number (f(vmax) >= f(BEST_VLOW) > 2^-44, obj >= BEST_OMIN), so the class's product is STRICTLY below
+// that of the class holding vmax: it neither wins nor ties.  Outside those conditions (every class logit below BEST_VLOW, a vanishing objectness under a threshold <= 0:
+// products underflow and tie at 0) nothing is filtered.
+constexpr float BEST_DELTA = 0.015625f, BEST_VCAP = 8.0f, BEST_VLOW = -30.0f, BEST_OMIN = 8.6736174e-19f /* 2^-60 */;
+__device__ __forceinline__ float best_class_cut(float vmax, float obj) {
+    if (!(vmax >= BEST_VLOW) || !(obj >= BEST_OMIN)) return -INFINITY;
+    return __fsub_rn(vmax < BEST_VCAP ? vmax : BEST_VCAP, BEST_DELTA);
+}
 
 // _utils.py:59-60: xy = (s*2 - 0.5 + grid) * stride ; wh = (s*2)**2 * anchor (each op rounded like torch's),
 // then box_convert cxcywh -> xyxy (box_head.py:358).  Inputs are the four raw box logits.

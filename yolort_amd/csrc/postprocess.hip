@@ -14,6 +14,15 @@
 // reference's torch.where order (box_head.py:418).  ~score_bits descends only for non-negative floats: that is the range of the in-plan producers
 // (decode_kernel, the head epilogue: sigmoid * sigmoid above a threshold), whose records are bit-inverted back into the score by the top-k gather.  The stand-alone
 // ymi_batched_nms takes ANY non-NaN float score (torchvision's contract) and builds its key with nms_score_key instead.
+//
+// Best-class mode (YMI_POST_BEST_CLASS in ymi_post_desc.flags; Python: multi_label=False).  The default above is yolort's multi-label PostProcess; this is the contract of
+// ultralytics' non_max_suppression(..., multi_label=False) (yolort/v5/utils/general.py:572-583, used by AutoShape), under which checkpoints ingested with load_from_yolov5
+// were trained and evaluated: per anchor conf = max_c s_c with s_c = fmul_rn(sigmoid(cls_c), sigmoid(obj)) -- the multi-label score, bit for bit --, label = the lowest class
+// with s_c == conf (torch.max(1)), candidate iff conf > score_thresh (strict), record lo = anchor << L | label: at most one record per anchor, status[4] = passing anchors.
+// Only the candidate producers know the mode (CandSink::best: decode_kernel here, the head epilogue in head_decode.hpp); sort (ties by anchor), class-aware NMS, top-k,
+// rescale, slab and status words are the ones above.  num_classes == 1: bit-identical to the default; thresholds <= 0: every anchor yields its best class.
+// Differences from ultralytics: the NMS is the true class-aware NMS of this file, not boxes offset by 4096 pixels per class; no max_nms = 30000 cut of the candidates;
+// scores stay fp32; `classes=` filtering and `agnostic=` are not part of it.
 #include "post_common.hpp"
 #include <cstdlib>
 
@@ -89,8 +98,54 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
             *reinterpret_cast<f32x4*>(k_.boxes_all + ((int64_t)img * k_.total_anchors + anchor) * 4) = b;
         }
         if (!any_obj) continue;
-        if (fill + nch > DEC_BUF || img != fill_img) flush();   // a pixel yields at most nch - 15 records
+        if (fill + (k_.best ? 3 : nch) > DEC_BUF || img != fill_img) flush();   // a pixel yields at most nch - 15 records (best-class mode: one per anchor)
         fill_img = img;
+        if (k_.best) {
+            // Best-class mode (wave-uniform branch): per anchor whose objectness passes, every lane keeps the best (score, class) of the channels it holds -- over all
+            // passes, so nch > 256 needs nothing else -- then a butterfly over the 64 lanes leaves the anchor's best pair in every lane.  "Best" is a total order
+            // (score descending, class ascending): the lowest class among equal PRODUCTS wins whatever the lane order.  Lane 0 writes the (at most three) records.
+            BestClass b0 = best_none(), b1 = best_none(), b2 = best_none();
+            for (int p = 0; p < npass; ++p) {
+                const int c0 = (p * 64 + lane) * 4;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (c0 + 3 < nch) v = *reinterpret_cast<const f32x4*>(row + c0);
+                else
+                    for (int e = 0; e < 4; ++e)
+                        if (c0 + e < nch) v[e] = row[c0 + e];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = c0 + e;
+                    const int k = c / a.K, cls = c - k * a.K - 5;
+                    const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
+                    if (c < nch && cls >= 0 && o > k_.thr) {
+                        const float s = __fmul_rn(sigmoid_acc(v[e]), o);   // the multi-label score, bit for bit
+                        BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
+                        if (best_before(s, cls, b)) b = BestClass{s, cls};
+                    }
+                }
+            }
+            int cnt = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (!(obj[k] > k_.thr)) continue;            // wave-uniform: every lane computed the same objectness
+                BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const BestClass t = {__shfl_xor(b.s, d, 64), __shfl_xor(b.c, d, 64)};
+                    if (best_before(t.s, t.c, b)) b = t;
+                }
+                if (b.c != 0x7fffffff && b.s > k_.thr) {    // conf > thr, strict (general.py:583)
+                    if (lane == 0) {
+                        const int anchor = a.level_off + (k * a.h + y) * a.w + x;
+                        bhi[fill + cnt] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(b.s));
+                        blo[fill + cnt] = ((unsigned)anchor << k_.label_bits) | (unsigned)b.c;
+                    }
+                    ++cnt;
+                }
+            }
+            fill += cnt;
+            continue;
+        }
         for (int p = 0; p < npass; ++p) {
             const int c0 = (p * 64 + lane) * 4;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};

@@ -52,8 +52,9 @@ def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence
 
 
 def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
-                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None) -> List[Dict[str, Tensor]]:
-    """Runs the fused post-process on reference-layout head outputs [(N,A,H,W,K)] (A == 3)."""
+                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True) -> List[Dict[str, Tensor]]:
+    """Runs the fused post-process on reference-layout head outputs [(N,A,H,W,K)] (A == 3).  multi_label=False: one label per anchor, its best class
+    (include/yolort_amd.h YMI_POST_BEST_CLASS)."""
     _lib.load(require_gpu=True)
     h0 = head_outputs[0]
     if not h0.is_cuda:
@@ -69,7 +70,7 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
         nhwc[..., : 3 * k] = ho.to(torch.float32).permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * k)
         plan_inputs.append(nhwc)
     cap = cand_cap or max(4096, 2048 * n)
-    flags = 0
+    flags = 0 if multi_label else _lib.POST_BEST_CLASS
     while True:
         plan = Plan(h0.device, torch.float16)
         views = [View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * k, t.shape[3]) for t in plan_inputs]
@@ -79,7 +80,7 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
         if st[1] == 0:
             break
         if not st[1] & 1:   # YMI_STATUS_PREFIX_SHORT only: the score prefix of a crowded image was too short, take everything
-            flags = _lib.POST_EXACT_FULL
+            flags |= _lib.POST_EXACT_FULL
             continue
         need = max(st[0], st[3] * n)     # st[3]: largest per-image count when the per-image sort path overflowed
         cap = max(int(need * 1.25) + 1024, 2 * cap)  # nothing is truncated silently: grow and redo
