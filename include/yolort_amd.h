@@ -287,8 +287,18 @@ typedef struct ymi_post_desc {
  * num_classes == 1 the two modes are bit-identical; thresholds <= 0 keep their meaning (every anchor yields its best class).  Honoured by ymi_postprocess,
  * ymi_conv_head_decode, ymi_conv_head_decode_group, their ymi_plan_add_* forms and the replay of an exported plan (the descriptor travels with the plan).
  * Differences from ultralytics: the NMS is the true class-aware NMS of this library, not the 4096-pixel class offset; there is no max_nms = 30000 cut of the
- * candidates; scores stay fp32; `classes=` filtering and `agnostic=` are not provided. */
+ * candidates; scores stay fp32; `classes=` filtering is not provided (`agnostic=` is YMI_POST_AGNOSTIC below). */
 #define YMI_POST_BEST_CLASS 2
+/* Class-agnostic NMS: ONE suppression over all candidates of an image, whatever their label -- ultralytics' non_max_suppression(..., agnostic=True), i.e.
+ * torchvision.ops.nms on the unshifted boxes.  Combines with YMI_POST_BEST_CLASS and YMI_POST_EXACT_FULL.  Candidate generation (both modes), the sort (score
+ * descending, ties by candidate index), top-k, rescale, slab, status words and the LABELS of the kept detections are unchanged; only the suppression changes: within
+ * an image a candidate is suppressed by ANY kept higher-ranked candidate whose fp32 IoU with it is > nms_thresh (strict; NaN from 0/0 does not suppress).  In
+ * multi-label mode the several classes of one anchor share a box (IoU 1), so only the best-scoring of them survives -- ultralytics behaves the same.  With
+ * num_classes == 1 the flag changes nothing in the result.  The score-prefix protocol holds as it is (decisions depend on higher-scored boxes only); more
+ * suppression makes YMI_STATUS_PREFIX_SHORT more frequent, and the re-run with YMI_POST_EXACT_FULL covers it.  Each image is walked by one workgroup
+ * (nms_block_kernel, csrc/postprocess.hip).  Honoured wherever YMI_POST_BEST_CLASS is: ymi_postprocess, ymi_post_finish (the fused head's begin / finish), the
+ * ymi_plan_add_* forms and the replay of an exported plan. */
+#define YMI_POST_AGNOSTIC 4
 #define YMI_STATUS_OVERFLOW_CAPACITY 1 /* status[1] bit 0: candidate capacity exceeded (grow cand_cap) */
 #define YMI_STATUS_PREFIX_SHORT 2      /* status[1] bit 1: prefix too short, re-run with YMI_POST_EXACT_FULL */
 
@@ -348,6 +358,9 @@ int ymi_conv_head_decode_group(const ymi_conv_desc* convs, int n_levels, const y
 int64_t ymi_nms_ws_bytes(int n);
 int ymi_batched_nms(const float* boxes, const float* scores, const int32_t* labels, int n, float nms_thresh,
                     int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);
+/* Stand-alone class-AGNOSTIC NMS of one image: torchvision.ops.nms -- ymi_batched_nms with every label equal, without the label array and the label sort, and with one
+ * workgroup instead of one wave walking the candidates.  Same buffers, same score contract (any non-NaN float, +-0 tie, n < 2^20), same workspace (ymi_nms_ws_bytes). */
+int ymi_nms(const float* boxes, const float* scores, int n, float nms_thresh, int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Plan: a recorded sequence of the launches above for one (arch, N, H, W, dtype), replayed with a

@@ -64,6 +64,7 @@ TAG_NONE, TAG_INPUT, TAG_RESCALE, TAG_BOXES, TAG_SCORES, TAG_LABELS, TAG_STATUS_
 ABI_VERSION = 6   # include/yolort_amd.h YMI_ABI_VERSION
 POST_EXACT_FULL = 1
 POST_BEST_CLASS = 2   # YMI_POST_BEST_CLASS: one label per anchor (ultralytics' multi_label=False)
+POST_AGNOSTIC = 4     # YMI_POST_AGNOSTIC: one NMS over all boxes of an image, whatever their label (ultralytics' agnostic=True)
 
 
 class PostDesc(C.Structure):
@@ -118,6 +119,7 @@ _SIGS = {
     "ymi_conv_head_decode": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PostDesc), C.c_int, C.c_void_p]),
     "ymi_nms_ws_bytes": (C.c_int64, [C.c_int]),
     "ymi_batched_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ymi_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

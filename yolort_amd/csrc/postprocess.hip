@@ -22,7 +22,11 @@
 // Only the candidate producers know the mode (CandSink::best: decode_kernel here, the head epilogue in head_decode.hpp); sort (ties by anchor), class-aware NMS, top-k,
 // rescale, slab and status words are the ones above.  num_classes == 1: bit-identical to the default; thresholds <= 0: every anchor yields its best class.
 // Differences from ultralytics: the NMS is the true class-aware NMS of this file, not boxes offset by 4096 pixels per class; no max_nms = 30000 cut of the candidates;
-// scores stay fp32; `classes=` filtering and `agnostic=` are not part of it.
+// scores stay fp32; `classes=` filtering is not part of it.
+//
+// Class-agnostic NMS (YMI_POST_AGNOSTIC in ymi_post_desc.flags; Python: agnostic=True; stand-alone: ymi_nms).  Candidates, sort, top-k, rescale, slab, status words and the
+// labels of the kept detections are those above; only the suppression changes: one greedy NMS over all candidates of an image (torchvision.ops.nms on the unshifted boxes,
+// ultralytics' agnostic=True).  The host keys P with label 0 -- P is G's order, a segment is an image -- and nms_block_kernel (section 3b) walks each segment with a workgroup.
 #include "post_common.hpp"
 #include <cstdlib>
 
@@ -897,6 +901,7 @@ constexpr int RANK_GRID = 1024; // blocks of the ranking kernel (they walk the p
 constexpr int RANK_NIMG = 1024; // images per batch the ranking kernel's per-block table holds; post_check_batch refuses a larger batch (there is no fallback)
 
 __device__ __forceinline__ uint64_t p_key_of(uint64_t g, int label_bits) {
+    if (label_bits == 0) return g;   // class-agnostic suppression (YMI_POST_AGNOSTIC): P is G's order
     return ((g & ((1ull << label_bits) - 1ull)) << (64 - label_bits)) | (g >> label_bits);
 }
 
@@ -1178,6 +1183,110 @@ __global__ __launch_bounds__(256) void nms_segments_kernel(const uint64_t* phi, 
 }
 
 // ------------------------------------------------------------------------------------------
+// 3b. class-AGNOSTIC NMS (YMI_POST_AGNOSTIC, ymi_nms): one segment per IMAGE, whatever the labels.  nms_segments_kernel would give the whole image to one
+//     wave -- the greedy scan of a crowded image on 1/1024 of the chip -- so here a segment gets a WORKGROUP of NMSB_WAVES waves.  The algorithm is the one
+//     above, step for step, hence bit-identical to it: candidates in score order, 64 per step; every wave holds the step's 64 candidates (lane l = candidate
+//     l) and tests them against ITS share of the kept list (kept boxes j = wave, wave + NMSB_WAVES, ...: LDS broadcast reads, the spill area beyond
+//     NMSB_KCAP); the per-wave alive masks meet in LDS; wave 0 ANDs them, resolves the 64 among themselves by ballot and shuffle, appends the survivors to
+//     the kept list and publishes the step's final mask.  Suppression is an OR over the kept boxes, so splitting the list over waves cannot change a bit.
+//     Two block barriers per step; every trip count of a loop with a barrier (segments, steps) comes from LDS words read after a barrier.
+// ------------------------------------------------------------------------------------------
+constexpr int NMSB_WAVES = 16;      // waves per segment (one 1024-thread block)
+constexpr int NMSB_KCAP = 2048;     // kept boxes of the block held in LDS (32 KiB); the rest spills to Workspace::kept_box
+
+__global__ __launch_bounds__(NMSB_WAVES * 64) void nms_block_kernel(const uint64_t* phi, const uint32_t* plo, const uint64_t* ghi, const uint32_t* glo,
+                                                                    const float* boxes_all, int total_anchors, int label_bits, const int* status, int cap,
+                                                                    const uint32_t* seg_start, float* kept_box, uint8_t* keep, float thr) {
+    __shared__ f32x4 kept_lds[NMSB_KCAP];
+    __shared__ uint64_t s_alive[NMSB_WAVES];
+    __shared__ uint64_t s_final;
+    __shared__ int s_nseg, s_neg_end;
+    (void)phi;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const int n = ncand(status, cap);
+    if (threadIdx.x == 0) s_nseg = status[ST_NSEG];
+    __syncthreads();
+    const int nseg = s_nseg;
+    for (int s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const int start = (int)seg_start[s];
+        // the segment ends at the smallest segment start behind its own (seg_start is unordered), or at n
+        if (threadIdx.x == 0) s_neg_end = -n;
+        __syncthreads();
+        for (int t = threadIdx.x; t < nseg; t += NMSB_WAVES * 64) {
+            const int o = (int)seg_start[t];
+            if (o > start) atomicMax(&s_neg_end, -o);
+        }
+        __syncthreads();
+        const int end = -s_neg_end;
+        const int nsteps = (end - start + 63) >> 6;
+        int kept_cnt = 0;
+        f32x4* kb = reinterpret_cast<f32x4*>(kept_box) + start;   // spill area: kept <= segment length
+        for (int st = 0; st < nsteps; ++st) {
+            const int p = start + st * 64 + lane;
+            const bool valid = p < end;
+            f32x4 box = {0.f, 0.f, 0.f, 0.f};
+            unsigned r = 0;
+            if (valid) {
+                r = plo[p];
+                const unsigned img = (unsigned)(ghi[r] >> 32);
+                const unsigned anchor = glo[r] >> label_bits;
+                box = *reinterpret_cast<const f32x4*>(boxes_all + ((int64_t)img * total_anchors + anchor) * 4);
+            }
+            const float area = __fmul_rn(__fsub_rn(box[2], box[0]), __fsub_rn(box[3], box[1]));
+            bool alive = valid;
+            // this wave's share of the boxes already kept (higher score)
+            const int in_lds = kept_cnt < NMSB_KCAP ? kept_cnt : NMSB_KCAP;
+            for (int j = wave; j < in_lds; j += NMSB_WAVES) {
+                const f32x4 k = kept_lds[j];
+                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
+                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
+            }
+            for (int j = NMSB_KCAP + wave; j < kept_cnt; j += NMSB_WAVES) {   // (NMSB_KCAP is a multiple of NMSB_WAVES)
+                const f32x4 k = kb[j];
+                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
+                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
+            }
+            const uint64_t mine = __ballot(alive);
+            if (lane == 0) s_alive[wave] = mine;
+            __syncthreads();
+            if (wave == 0) {
+                uint64_t mask = s_alive[0];
+#pragma unroll
+                for (int w = 1; w < NMSB_WAVES; ++w) mask &= s_alive[w];
+                alive = (mask >> lane) & 1ull;
+                // among the 64 candidates of this step, in order
+                uint64_t todo = mask;
+                while (todo) {
+                    const int i = __ffsll((long long)todo) - 1;
+                    todo &= todo - 1;
+                    f32x4 bi;
+                    bi[0] = __shfl(box[0], i, 64);
+                    bi[1] = __shfl(box[1], i, 64);
+                    bi[2] = __shfl(box[2], i, 64);
+                    bi[3] = __shfl(box[3], i, 64);
+                    const float ai = __shfl(area, i, 64);
+                    if (alive && lane > i && iou_gt(bi, ai, box, area, thr)) alive = false;
+                    mask = __ballot(alive);
+                    todo &= mask;
+                }
+                if (alive) {
+                    const int slot = kept_cnt + __popcll(mask & lt);
+                    if (slot < NMSB_KCAP) kept_lds[slot] = box; else kb[slot] = box;
+                    keep[r] = 1;
+                }
+                if (lane == 0) s_final = mask;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // kept boxes (LDS / HBM) visible to the block's later reads
+            }
+            __syncthreads();
+            kept_cnt += __popcll(s_final);
+        }
+        __syncthreads();   // the last step's s_final / this segment's s_neg_end have been read by every wave before the next segment resets them
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // 4. top-k + rescale.  One block per image: binary-search the image's range in G, then an ordered
 //    compaction of the keep flags in rank order; first K kept are written to the fixed slab.
 // ------------------------------------------------------------------------------------------
@@ -1306,16 +1415,28 @@ static int radix_pass(const Workspace& w, SortState& st, int* status, int cap, i
     return check_launch("radix pass");
 }
 
-// segments -> class-aware NMS -> top-k gather, given G (arrays w.hi/lo[g]) and the per-class order P
+// YOLORT_AMD_NMS_BLOCK (default 1; read once per process): 0 sends the class-agnostic segments -- P keyed with label 0 -- through nms_segments_kernel, one wave per image:
+// the bit-identical counterpart of nms_block_kernel, for tests and A/B
+static bool nms_block_enabled() {
+    static const bool on = getenv("YOLORT_AMD_NMS_BLOCK") ? atoi(getenv("YOLORT_AMD_NMS_BLOCK")) != 0 : true;
+    return on;
+}
+
+// segments -> NMS -> top-k gather, given G (arrays w.hi/lo[g]) and the order P the NMS walks: per (image, class) by default, per image (== G's order, every record keyed
+// with label 0) under YMI_POST_AGNOSTIC, where a segment gets a workgroup (nms_block_kernel) instead of a wave
 static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint32_t* plo, int* status, int cap, int n_img, int label_bits, int total_anchors,
                       float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count, hipStream_t s,
-                      const int* truncated = nullptr, float* out_slab = nullptr, const int* img_count = nullptr) {
+                      const int* truncated = nullptr, float* out_slab = nullptr, const int* img_count = nullptr, bool agnostic = false) {
     const int nthr_blocks = cdiv(cap, 256);
     uint32_t* seg_start = w.seg_start;
     float* kept_box = w.kept_box;
     hipLaunchKernelGGL(find_segments_kernel, dim3(nthr_blocks), dim3(256), 0, s, phi, status, cap, seg_start);
-    hipLaunchKernelGGL(nms_segments_kernel, dim3(1024), dim3(256), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
-                       seg_start, kept_box, w.keep, nms_thresh);
+    if (agnostic && nms_block_enabled())   // at most n_img segments
+        hipLaunchKernelGGL(nms_block_kernel, dim3(n_img), dim3(NMSB_WAVES * 64), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
+                           seg_start, kept_box, w.keep, nms_thresh);
+    else
+        hipLaunchKernelGGL(nms_segments_kernel, dim3(1024), dim3(256), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
+                           seg_start, kept_box, w.keep, nms_thresh);
     GatherArgs ga;
     ga.ghi = w.hi[g]; ga.glo = w.lo[g]; ga.keep = w.keep; ga.boxes_all = w.boxes_all; ga.rescale = rescale; ga.status = status;
     ga.truncated = truncated; ga.status_rw = status; ga.out_slab = out_slab; ga.img_count = img_count;
@@ -1328,7 +1449,7 @@ static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint
 // sorts records in w.hi/lo[st.cur] by (img, score desc, cand asc), then runs NMS + gather.
 static int sort_nms_gather(const Workspace& w, SortState st, int* status, int cap, int n_img, int lo_bits, int label_bits, int total_anchors,
                            float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count,
-                           hipStream_t s, float* out_slab = nullptr) {
+                           hipStream_t s, float* out_slab = nullptr, bool agnostic = false) {
     int rc;
     for (int sh = 0; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
     for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
@@ -1337,7 +1458,8 @@ static int sort_nms_gather(const Workspace& w, SortState st, int* status, int ca
     // G = current arrays; P = the other pair, re-keyed by label
     const int g = st.cur, p = st.cur ^ 1;
     const int nthr_blocks = cdiv(cap, 256);
-    hipLaunchKernelGGL(make_label_records_kernel, dim3(nthr_blocks), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, cap, label_bits, w.keep);
+    const int p_bits = agnostic ? 0 : label_bits;   // class-agnostic: every record is keyed with label 0 and no label pass follows -- P is G's order, segments are images
+    hipLaunchKernelGGL(make_label_records_kernel, dim3(nthr_blocks), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, cap, p_bits, w.keep);
     // The label passes ping-pong between P and a scratch pair; G must stay intact, so P's partner
     // arrays are carved from seg_start/kept_box which are not live yet.
     Workspace wl = w;
@@ -1347,7 +1469,7 @@ static int sort_nms_gather(const Workspace& w, SortState st, int* status, int ca
     wl.lo[1] = w.seg_start;                                   // cap * 4 bytes
     SortState sl{0};
     int label_passes = 0;
-    for (int sh = 32; sh < 32 + label_bits; sh += 8) {
+    for (int sh = 32; sh < 32 + p_bits; sh += 8) {
         if ((rc = radix_pass(wl, sl, status, cap, sh, s)) != YMI_OK) return rc;
         ++label_passes;
     }
@@ -1361,7 +1483,8 @@ static int sort_nms_gather(const Workspace& w, SortState st, int* status, int ca
         plo = w.lo[p];
     }
     (void)label_passes;
-    return nms_gather(w, g, phi, plo, status, cap, n_img, label_bits, total_anchors, nms_thresh, K, rescale, out_boxes, out_scores, out_labels, out_count, s, nullptr, out_slab);
+    return nms_gather(w, g, phi, plo, status, cap, n_img, label_bits, total_anchors, nms_thresh, K, rescale, out_boxes, out_scores, out_labels, out_count, s, nullptr, out_slab,
+                      nullptr, agnostic);
 }
 
 // The batch size a descriptor may carry: the per-image path ranks the whole batch through one LDS table (rank_image_kernel), and include/yolort_amd.h gives that limit
@@ -1440,6 +1563,8 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
     Workspace w;
     int rc = post_validate(d, false, L, w);
     if (rc != YMI_OK) return rc;
+    const bool agnostic = (d->flags & YMI_POST_AGNOSTIC) != 0;
+    const int p_bits = agnostic ? 0 : L.label_bits;   // label bits of the P keys: none under YMI_POST_AGNOSTIC (P is G's order, one segment per image)
     if (L.per_image) {
         const int cap_img = L.cap_img;
         const bool exact_full = (d->flags & YMI_POST_EXACT_FULL) != 0;
@@ -1474,8 +1599,8 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
         }
         const int rank_cap = cap_img < RANK_MAX ? cap_img : RANK_MAX;   // no image holds more than cap_img records
         hipLaunchKernelGGL(rank_image_kernel, dim3(RANK_GRID), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.sel_count, d->n, cap_img,
-                           L.label_bits, rank_g, rank_p);
-        hipLaunchKernelGGL(scatter_ranks_kernel, dim3(cdiv(rank_cap, RANK_IT), d->n), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, L.label_bits,
+                           p_bits, rank_g, rank_p);
+        hipLaunchKernelGGL(scatter_ranks_kernel, dim3(cdiv(rank_cap, RANK_IT), d->n), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, p_bits,
                            rank_g, rank_p, w.hi[1], w.lo[1], w.p_hi, w.p_lo, w.keep, d->status);
         // LDS run length of the sort: with the prefix selection images rarely exceed 8192 records (longer ones take the
         // multi-run merge path), and 64 KiB instead of 128 leaves room for a convolution block on the same CU
@@ -1485,17 +1610,17 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
         if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)sort_image_kernel, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
         // the producers wrote arrays [0] (per-image regions); G goes to arrays [1] (compact), P to its own pair
         if (cap_img > RANK_MAX)   // only then can an image exceed the ranking path
-            hipLaunchKernelGGL(sort_image_kernel, dim3(d->n), dim3(1024), lds, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, d->n, L.label_bits, lds_keys,
+            hipLaunchKernelGGL(sort_image_kernel, dim3(d->n), dim3(1024), lds, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, d->n, p_bits, lds_keys,
                                RANK_MAX, w.hi[1], w.lo[1], w.p_hi, w.p_lo, w.keep, d->status);
         if ((rc = check_launch("select_prefix/sort_image")) != YMI_OK) return rc;
         return nms_gather(w, 1, w.p_hi, w.p_lo, d->status, d->cand_cap, d->n, L.label_bits, L.total_anchors, d->nms_thresh, d->detections_per_img, d->rescale,
-                          d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, w.sel_count + d->n, d->out_slab, w.img_count);
+                          d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, w.sel_count + d->n, d->out_slab, w.img_count, agnostic);
     }
     hipLaunchKernelGGL(finalize_count_kernel, dim3(1), dim3(64), 0, s, d->status, d->cand_cap);
     rc = check_launch("finalize_count");
     if (rc != YMI_OK) return rc;
     return sort_nms_gather(w, SortState{0}, d->status, d->cand_cap, d->n, L.label_bits + L.anchor_bits, L.label_bits, L.total_anchors, d->nms_thresh,
-                           d->detections_per_img, d->rescale, d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, d->out_slab);
+                           d->detections_per_img, d->rescale, d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, d->out_slab, agnostic);
 }
 
 int postprocess_launch(const ymi_post_desc* d, hipStream_t s) {
@@ -1524,7 +1649,7 @@ __global__ __launch_bounds__(256) void nms_make_records_kernel(const float* boxe
     if (i >= n) return;
     *reinterpret_cast<f32x4*>(boxes_all + (int64_t)i * 4) = *reinterpret_cast<const f32x4*>(boxes + (int64_t)i * 4);
     hi[i] = (uint64_t)nms_score_key(scores[i]);
-    lo[i] = ((unsigned)i << NMS_LABEL_BITS) | ((unsigned)labels[i] & ((1u << NMS_LABEL_BITS) - 1u));
+    lo[i] = ((unsigned)i << NMS_LABEL_BITS) | (labels != nullptr ? (unsigned)labels[i] & ((1u << NMS_LABEL_BITS) - 1u) : 0u);   // labels == NULL: ymi_nms
 }
 
 __global__ __launch_bounds__(256) void nms_emit_keep_kernel(const uint32_t* glo, const uint8_t* keep, int n, int* keep_out, int* count_out) {
@@ -1609,4 +1734,36 @@ extern "C" int ymi_batched_nms(const float* boxes, const float* scores, const in
                        w.kept_box, w.keep, nms_thresh);
     hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(1), dim3(256), 0, s, w.lo[g], w.keep, n, keep_out, count_out);
     return check_launch("ymi_batched_nms");
+}
+
+// torchvision.ops.nms: ymi_batched_nms's sequence with every record keyed with label 0 -- no label passes, ONE segment -- and the workgroup-per-segment kernel
+extern "C" int ymi_nms(const float* boxes, const float* scores, int n, float nms_thresh, int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    YMI_REQUIRE(count_out && ws, "ymi_nms: null buffer");
+    if (n == 0) {
+        YMI_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int), s));
+        return YMI_OK;
+    }
+    YMI_REQUIRE(boxes && scores && keep_out, "ymi_nms: null buffer");
+    YMI_REQUIRE(n > 0 && n < (1 << (32 - NMS_LABEL_BITS)), "ymi_nms: n=%d out of range (max %d)", n, (1 << (32 - NMS_LABEL_BITS)) - 1);
+    YMI_REQUIRE(ws_bytes >= ymi_nms_ws_bytes(n), "ymi_nms: workspace too small");
+    int* status = (int*)ws;
+    const Workspace w = carve((char*)ws + 256, 1, n, n);
+    hipLaunchKernelGGL(nms_make_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, boxes, scores, (const int*)nullptr, n, w.boxes_all, w.hi[0], w.lo[0], status);
+    int rc;
+    SortState st{0};
+    const int lo_bits = NMS_LABEL_BITS + bits_for(n);
+    for (int sh = NMS_LABEL_BITS; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;   // (the label field is zero: nothing to sort below it)
+    for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;
+    const int g = st.cur, p = st.cur ^ 1;
+    hipLaunchKernelGGL(make_label_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, n, 0, w.keep);   // P = G's order, one key
+    hipLaunchKernelGGL(find_segments_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w.hi[p], status, n, w.seg_start);
+    if (nms_block_enabled())
+        hipLaunchKernelGGL(nms_block_kernel, dim3(1), dim3(NMSB_WAVES * 64), 0, s, w.hi[p], w.lo[p], w.hi[g], w.lo[g], w.boxes_all, n, NMS_LABEL_BITS, status, n, w.seg_start,
+                           w.kept_box, w.keep, nms_thresh);
+    else
+        hipLaunchKernelGGL(nms_segments_kernel, dim3(1), dim3(256), 0, s, w.hi[p], w.lo[p], w.hi[g], w.lo[g], w.boxes_all, n, NMS_LABEL_BITS, status, n, w.seg_start,
+                           w.kept_box, w.keep, nms_thresh);
+    hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(1), dim3(256), 0, s, w.lo[g], w.keep, n, keep_out, count_out);
+    return check_launch("ymi_nms");
 }

@@ -108,11 +108,13 @@ class PostProcess(nn.Module):
     """Same constructor as the reference (box_head.py:376-389), plus `multi_label`: True (default) is the reference's multi-label contract -- every (anchor, class)
     pair above the threshold is a candidate (box_head.py:418); False is the contract of ultralytics' non_max_suppression(..., multi_label=False)
     (yolort/v5/utils/general.py:572-583, what AutoShape uses): an anchor yields at most one detection, its class with the largest cls * obj (the lowest index among
-    equal products).  An attribute of a live model: flipping it takes effect on the next batch."""
+    equal products).  An attribute of a live model: flipping it takes effect on the next batch.  `agnostic` (default False; ultralytics' agnostic=True): one NMS over all
+    boxes of an image, whatever their label -- torchvision.ops.nms on the unshifted boxes; labels of the kept detections are unchanged.  Also a live attribute."""
 
-    def __init__(self, strides: List[int], score_thresh: float, nms_thresh: float, detections_per_img: int, multi_label: bool = True) -> None:
+    def __init__(self, strides: List[int], score_thresh: float, nms_thresh: float, detections_per_img: int, multi_label: bool = True, agnostic: bool = False) -> None:
         super().__init__()
         self.multi_label = multi_label
+        self.agnostic = agnostic
         self.strides = strides
         self.score_thresh = score_thresh
         self.nms_thresh = nms_thresh
@@ -129,4 +131,4 @@ class PostProcess(nn.Module):
             anchors.append(a)
         k = head_outputs[0].shape[-1]
         return postprocess_logits(head_outputs, [float(s) for s in self.strides], anchors, k - 5, self.score_thresh, self.nms_thresh, self.detections_per_img,
-                                  multi_label=self.multi_label)
+                                  multi_label=self.multi_label, agnostic=self.agnostic)

@@ -14,7 +14,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 import torch
 from torch import Tensor, nn
 
-from .._lib import POST_BEST_CLASS, POST_EXACT_FULL, YmiError, check
+from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_EXACT_FULL, YmiError, check
 from ..engine import Plan, View
 from ..hipmodule import compute_dtype_of, nchw_to_view, view_to_nchw, weights_signature
 from ..ops import slab_to_list
@@ -171,6 +171,7 @@ class YOLO(nn.Module):
         detections_per_img: int = 300,
         post_process: Optional[nn.Module] = None,
         multi_label: bool = True,
+        agnostic: bool = False,
     ):
         super().__init__()
         if not hasattr(backbone, "out_channels"):
@@ -185,7 +186,7 @@ class YOLO(nn.Module):
         self.compute_loss = criterion  # training criterion is out of scope; kept only if the caller injects one
         self.num_classes = num_classes
         self.head = head if head is not None else YOLOHead(backbone.out_channels, self.anchor_generator.num_anchors, self.anchor_generator.strides, num_classes)
-        self.post_process = post_process if post_process is not None else PostProcess(self.anchor_generator.strides, score_thresh, nms_thresh, detections_per_img, multi_label=multi_label)
+        self.post_process = post_process if post_process is not None else PostProcess(self.anchor_generator.strides, score_thresh, nms_thresh, detections_per_img, multi_label=multi_label, agnostic=agnostic)
         self.compute_dtype = torch.float16  # used when parameters are fp32 (see hipmodule.compute_dtype_of)
         # the conv stack of a batch is replayed as ONE captured hipGraph launch (csrc/api.cpp ymi_plan_run: captured once per plan instance and op range) instead of ~45
         # kernel launches from the host: same kernels, same order, same results (tests/test_boundary_gpu.py), 0.12 ms less host time per batch (profiles/r04n_pipeline_depth_graph.txt).
@@ -267,9 +268,9 @@ class YOLO(nn.Module):
 
     def _post_key(self) -> Optional[Tuple]:
         """the post-process settings a recorded plan has baked in (part of the plan key, fused and unfused head alike): changing one of them on a live model -- the
-        mode `multi_label` included -- must not meet a plan recorded for the old value"""
+        modes `multi_label` and `agnostic` included -- must not meet a plan recorded for the old value"""
         pp = self.post_process
-        return (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True))) if self.fused() else None
+        return (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True)), bool(getattr(pp, "agnostic", False))) if self.fused() else None
 
     def _entry(self, n: int, h: int, w: int, device: torch.device) -> _PlanEntry:
         """a plan instance of this shape whose previous batch has been collected by the host.  Instances are built lazily
@@ -350,7 +351,7 @@ class YOLO(nn.Module):
             ag = self.anchor_generator
             strides = [float(s) for s in ag.strides]
             args = (self.num_classes, float(pp.score_thresh), float(pp.nms_thresh), int(pp.detections_per_img), self.cand_cap_per_image * n)
-            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS)   # rebuilt plans (capacity growth, exact full pass) come through here too
+            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0)   # rebuilt plans (capacity growth, exact full pass) come through here too
             if self.fuse_head_decode and self.head.can_fuse_decode(plan, feats):
                 post, pd = plan.post_desc([(f.h, f.w) for f in feats], n, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
                 plan.post_begin(pd)
@@ -520,7 +521,7 @@ class YOLO(nn.Module):
 
     @classmethod
     def load_from_yolov5(cls, checkpoint_path: str, score_thresh: float = 0.25, nms_thresh: float = 0.45, version: str = "r6.0",
-                         post_process: Optional[nn.Module] = None, multi_label: bool = True):
+                         post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False):
         """Load model state from a checkpoint trained by ultralytics/yolov5 (reference yolo.py:185-223)."""
         from ._checkpoint import load_from_ultralytics
 
@@ -528,7 +529,7 @@ class YOLO(nn.Module):
         backbone_name = f"darknet_{info['size']}_{version.replace('.', '_')}"
         backbone = darknet_pan_backbone(backbone_name, info["depth_multiple"], info["width_multiple"], version=version, use_p6=info["use_p6"])
         model = cls(backbone, info["num_classes"], strides=info["strides"], anchor_grids=info["anchor_grids"], score_thresh=score_thresh,
-                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label)
+                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic)
         model.load_state_dict(info["state_dict"])
         return model
 

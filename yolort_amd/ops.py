@@ -43,6 +43,25 @@ def batched_nms(boxes: Tensor, scores: Tensor, labels: Tensor, iou_threshold: fl
     return keep[:k].to(torch.int64)
 
 
+def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
+    """torchvision.ops.nms on the MI355X: greedy suppression over ALL boxes (no classes), IoU > iou_threshold strict, fp32; returns kept indices (int64) in
+    score-descending stable order.  The score contract is batched_nms's (any non-NaN float, -0.0 and +0.0 tie, the lower index first); at most 2^20 - 1 boxes per call.
+    One workgroup walks the boxes (ymi_nms, include/yolort_amd.h); no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    if not boxes.is_cuda or not scores.is_cuda:
+        raise YmiError("nms runs on an MI355X only (no CPU fallback)")
+    n = int(scores.numel())
+    dev = boxes.device
+    b = boxes.detach().to(torch.float32).contiguous()
+    s = scores.detach().to(torch.float32).contiguous()
+    keep = torch.empty(max(n, 1), device=dev, dtype=torch.int32)
+    count = torch.zeros(1, device=dev, dtype=torch.int32)
+    ws = torch.empty(lib.ymi_nms_ws_bytes(n), device=dev, dtype=torch.uint8)
+    check(lib.ymi_nms(b.data_ptr(), s.data_ptr(), n, float(iou_threshold), keep.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "ymi_nms")
+    k = int(count.item())
+    return keep[:k].to(torch.int64)
+
+
 def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence[int]) -> List[Dict[str, Tensor]]:
     """Fixed (N,K,..) slab -> the reference's List[Dict] with keys in its order (box_head.py:427)."""
     out = []
@@ -52,9 +71,9 @@ def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence
 
 
 def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
-                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True) -> List[Dict[str, Tensor]]:
+                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True, agnostic: bool = False) -> List[Dict[str, Tensor]]:
     """Runs the fused post-process on reference-layout head outputs [(N,A,H,W,K)] (A == 3).  multi_label=False: one label per anchor, its best class
-    (include/yolort_amd.h YMI_POST_BEST_CLASS)."""
+    (include/yolort_amd.h YMI_POST_BEST_CLASS).  agnostic=True: one NMS over all boxes of an image, whatever their label (YMI_POST_AGNOSTIC)."""
     _lib.load(require_gpu=True)
     h0 = head_outputs[0]
     if not h0.is_cuda:
@@ -70,7 +89,7 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
         nhwc[..., : 3 * k] = ho.to(torch.float32).permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * k)
         plan_inputs.append(nhwc)
     cap = cand_cap or max(4096, 2048 * n)
-    flags = 0 if multi_label else _lib.POST_BEST_CLASS
+    flags = (0 if multi_label else _lib.POST_BEST_CLASS) | (_lib.POST_AGNOSTIC if agnostic else 0)
     while True:
         plan = Plan(h0.device, torch.float16)
         views = [View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * k, t.shape[3]) for t in plan_inputs]

@@ -4,7 +4,7 @@
 // test/tracing/test_tracing.cpp:4-5).  This translation unit is the same plug point for this repo: linked (or dlopen'ed) into a LibTorch program it registers
 //     yolort_amd::nms(Tensor dets, Tensor scores, float iou_threshold) -> Tensor            (torchvision::nms semantics, box_head.py:422 -> torchvision.ops)
 //     yolort_amd::batched_nms(Tensor boxes, Tensor scores, Tensor idxs, float iou_threshold) -> Tensor
-// for the CUDA (= HIP on ROCm) dispatch key, implemented by the C ABI (`ymi_batched_nms`, include/yolort_amd.h) -- no CPU kernel is registered: off-GPU calls fail in the
+// for the CUDA (= HIP on ROCm) dispatch key, implemented by the C ABI (`ymi_nms` / `ymi_batched_nms`, include/yolort_amd.h) -- no CPU kernel is registered: off-GPU calls fail in the
 // dispatcher, like everything else in this package.  It is NOT part of libyolort_amd.so (the C-ABI library stays free of torch types); build it on demand with
 // `python -m yolort_amd.torch_ext` (torch.utils.cpp_extension, in-tree output yolort_amd/lib/libyolort_amd_torch.so) or with the two lines of INTEGRATION.md section 3.
 #include <ATen/ATen.h>
@@ -39,7 +39,19 @@ at::Tensor batched_nms(const at::Tensor& boxes, const at::Tensor& scores, const 
 }
 
 at::Tensor nms(const at::Tensor& dets, const at::Tensor& scores, double iou_threshold) {
-    return batched_nms(dets, scores, at::zeros({dets.size(0)}, dets.options().dtype(at::kInt)), iou_threshold);
+    TORCH_CHECK(dets.is_cuda() && scores.is_cuda(), "yolort_amd::nms runs on an MI355X only (no CPU fallback)");
+    TORCH_CHECK(dets.dim() == 2 && dets.size(1) == 4 && scores.dim() == 1 && scores.size(0) == dets.size(0), "yolort_amd::nms: dets (n, 4), scores (n) expected");
+    const c10::hip::HIPGuard guard(dets.device().index());
+    const int64_t n = dets.size(0);
+    if (n == 0) return at::empty({0}, dets.options().dtype(at::kLong));
+    const at::Tensor b = dets.to(at::kFloat).contiguous(), s = scores.to(at::kFloat).contiguous();
+    at::Tensor keep = at::empty({n}, dets.options().dtype(at::kInt));
+    at::Tensor count = at::zeros({1}, dets.options().dtype(at::kInt));
+    at::Tensor ws = at::empty({ymi_nms_ws_bytes((int)n)}, dets.options().dtype(at::kByte));
+    const int rc = ymi_nms(b.data_ptr<float>(), s.data_ptr<float>(), (int)n, (float)iou_threshold, keep.data_ptr<int32_t>(), count.data_ptr<int32_t>(), ws.data_ptr(), ws.numel(),
+                           c10::hip::getCurrentHIPStream().stream());
+    TORCH_CHECK(rc == 0, "ymi_nms failed: ", ymi_last_error());
+    return keep.narrow(0, 0, count.item<int32_t>()).to(at::kLong);
 }
 
 }  // namespace
