@@ -287,7 +287,7 @@ typedef struct ymi_post_desc {
  * num_classes == 1 the two modes are bit-identical; thresholds <= 0 keep their meaning (every anchor yields its best class).  Honoured by ymi_postprocess,
  * ymi_conv_head_decode, ymi_conv_head_decode_group, their ymi_plan_add_* forms and the replay of an exported plan (the descriptor travels with the plan).
  * Differences from ultralytics: the NMS is the true class-aware NMS of this library, not the 4096-pixel class offset; there is no max_nms = 30000 cut of the
- * candidates; scores stay fp32; `classes=` filtering is not provided (`agnostic=` is YMI_POST_AGNOSTIC below). */
+ * candidates; scores stay fp32 (`agnostic=` is YMI_POST_AGNOSTIC, `classes=` is YMI_POST_CLASS_FILTER below). */
 #define YMI_POST_BEST_CLASS 2
 /* Class-agnostic NMS: ONE suppression over all candidates of an image, whatever their label -- ultralytics' non_max_suppression(..., agnostic=True), i.e.
  * torchvision.ops.nms on the unshifted boxes.  Combines with YMI_POST_BEST_CLASS and YMI_POST_EXACT_FULL.  Candidate generation (both modes), the sort (score
@@ -299,6 +299,21 @@ typedef struct ymi_post_desc {
  * (nms_block_kernel, csrc/postprocess.hip).  Honoured wherever YMI_POST_BEST_CLASS is: ymi_postprocess, ymi_post_finish (the fused head's begin / finish), the
  * ymi_plan_add_* forms and the replay of an exported plan. */
 #define YMI_POST_AGNOSTIC 4
+/* Class filter: only detections of an allowed set of classes -- ultralytics' non_max_suppression(..., classes=[...]) (yolort/v5/utils/general.py:585-587: after the
+ * candidates are generated, before NMS).  Combines with YMI_POST_EXACT_FULL, YMI_POST_BEST_CLASS and YMI_POST_AGNOSTIC.  The set is a bit set in the workspace
+ * (uint32[128] at ymi_post_class_mask_offset: bit c & 31 of word c >> 5 set = class c allowed), written by ymi_post_set_classes / ymi_plan_set_classes or by the
+ * consumer, and read by the candidate producers only -- so changing the SET needs no new descriptor, no re-record and no graph re-capture; only switching between
+ * "no filter" and "filter" changes the flag.  The region is carved last (every other workspace offset is unchanged); ymi_post_begin never touches it, and a fresh
+ * workspace holds no valid mask: write it before the first run.
+ *   multi-label mode: an (anchor, class) pair is a candidate iff cls * obj > score_thresh (strict, as ever) AND the class is allowed.
+ *   best-class mode:  the best class is taken over ALL classes exactly as without the filter; the anchor is a candidate iff that class passes the threshold AND is
+ *                     allowed.  An anchor whose best class is not allowed yields nothing even if an allowed class passes (ultralytics filters after x[:, 5:].max(1)).
+ *   agnostic:         the single suppression runs over the filtered candidates only (a box of an unwanted class suppresses nothing).
+ * The empty set gives zero detections in every image; with num_classes == 1 the set {0} is bit-identical to no filter.  Records of allowed classes are bit-identical to
+ * those of an unfiltered run; sort, NMS, top-k, rescale and slab are unchanged.  status[4] counts what was produced AFTER the filter (passing pairs of allowed classes /
+ * passing anchors whose best class is allowed); the capacity and score-prefix protocols apply to the filtered records.  Honoured wherever YMI_POST_BEST_CLASS is:
+ * ymi_postprocess, ymi_conv_head_decode, ymi_conv_head_decode_group, their ymi_plan_add_* forms and the replay of an exported plan. */
+#define YMI_POST_CLASS_FILTER 8
 #define YMI_STATUS_OVERFLOW_CAPACITY 1 /* status[1] bit 0: candidate capacity exceeded (grow cand_cap) */
 #define YMI_STATUS_PREFIX_SHORT 2      /* status[1] bit 1: prefix too short, re-run with YMI_POST_EXACT_FULL */
 
@@ -336,6 +351,14 @@ int ymi_postprocess(const ymi_post_desc* d, void* stream);
  * begin / finish / ymi_conv_head_decode; lh / lw / stride / anchors describe the levels as before. */
 int ymi_post_begin(const ymi_post_desc* d, void* stream);
 int ymi_post_finish(const ymi_post_desc* d, void* stream);
+
+/* YMI_POST_CLASS_FILTER: byte offset of the class mask (uint32[128], 256-byte aligned) inside a workspace of ymi_postprocess_ws_bytes(n, total_anchors, cand_cap)
+ * bytes, for consumers who write the mask themselves; negative for arguments that have no workspace. */
+int64_t ymi_post_class_mask_offset(int n, int total_anchors, int cand_cap);
+/* writes the mask of descriptor d's workspace on `stream`: classes[0 .. count) are the allowed class indices (any order, duplicates allowed, count == 0 = the empty
+ * set), each 0 <= c < d->num_classes, else YMI_EINVAL and nothing is written.  The list is consumed before the call returns (the words travel by value in a kernel
+ * argument), the write is ordered on `stream` like any launch and may be captured.  YMI_EINVAL when d->flags lacks YMI_POST_CLASS_FILTER. */
+int ymi_post_set_classes(const ymi_post_desc* d, const int32_t* classes, int count, void* stream);
 
 /* Detection head of pyramid level `level` (the biased 1x1 conv of yolort/models/box_head.py:36,74) with the
  * decode + sigmoid + multi-label threshold of box_head.py:345-360,414-418 and _utils.py:59-60 fused into the
@@ -385,6 +408,12 @@ int ymi_plan_add_head_decode(ymi_plan* p, const ymi_conv_desc* conv, const ymi_p
 int ymi_plan_add_head_decode_group(ymi_plan* p, const ymi_conv_desc* convs, int n_levels, const ymi_post_desc* d);
 int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d);
 int ymi_plan_num_ops(const ymi_plan* p);
+/* ymi_post_set_classes for every post-process descriptor recorded in the plan that carries YMI_POST_CLASS_FILTER (YMI_EINVAL if none does).  The plan remembers the
+ * list: ymi_plan_export stores it, and ymi_plan_import writes the masks again before it returns, so an imported plan filters as the exporting one did; the consumer
+ * changes the set later with this call.  A plan exported without a list imports with the empty set (its workspace is zero-filled).  ymi_plan_import has no stream
+ * of the caller's: it writes the masks on the NULL (legacy default) stream and calls hipStreamSynchronize on it before it returns -- a consumer whose other threads
+ * use blocking streams sees that synchronisation; streams created with hipStreamNonBlocking are not waited for. */
+int ymi_plan_set_classes(ymi_plan* p, const int32_t* classes, int count, void* stream);
 /* on != 0: ops 0 and 1 (the stem over the letterboxed canvas and body.1 reading its output, see ymi_stem_body1) run as ONE launch whenever a
  * run covers both; op indices are unchanged, the stem's output buffer is then not written.  Fails unless ops 0 and 1 are such a pair. */
 int ymi_plan_set_fuse_stem(ymi_plan* p, int on);

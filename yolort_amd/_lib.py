@@ -65,6 +65,7 @@ ABI_VERSION = 6   # include/yolort_amd.h YMI_ABI_VERSION
 POST_EXACT_FULL = 1
 POST_BEST_CLASS = 2   # YMI_POST_BEST_CLASS: one label per anchor (ultralytics' multi_label=False)
 POST_AGNOSTIC = 4     # YMI_POST_AGNOSTIC: one NMS over all boxes of an image, whatever their label (ultralytics' agnostic=True)
+POST_CLASS_FILTER = 8  # YMI_POST_CLASS_FILTER: only candidates of the classes in the workspace's mask (ultralytics' classes=[...])
 
 
 class PostDesc(C.Structure):
@@ -115,6 +116,9 @@ _SIGS = {
     "ymi_postprocess": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
     "ymi_post_begin": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
     "ymi_post_finish": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
+    "ymi_post_class_mask_offset": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "ymi_post_set_classes": (C.c_int, [C.POINTER(PostDesc), C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
+    "ymi_plan_set_classes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "ymi_conv_head_decode_group": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(PostDesc), C.c_void_p]),
     "ymi_conv_head_decode": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(PostDesc), C.c_int, C.c_void_p]),
     "ymi_nms_ws_bytes": (C.c_int64, [C.c_int]),
@@ -175,6 +179,32 @@ def check(rc: int, what: str = "") -> None:
     if rc < 0:
         msg = _lib.ymi_last_error().decode("utf-8", "replace") if _lib is not None else ""
         raise YmiError(f"{what or 'libyolort_amd'} failed (code {rc}): {msg}")
+
+
+def normalize_classes(classes, num_classes: Optional[int] = None):
+    """the `classes=` argument of the post-process (ultralytics' non_max_suppression(..., classes=...)): None = no filter, else an iterable of class indices -> a sorted
+    tuple without duplicates (order and repeats are irrelevant to a set).  ValueError for a non-integer, a negative index or, when `num_classes` is known, one >= it."""
+    if classes is None:
+        return None
+    import operator
+    if isinstance(classes, (str, bytes)):
+        raise ValueError(f"classes must be an iterable of class indices, got {classes!r}")
+    out = set()
+    try:
+        items = list(classes)
+    except TypeError:
+        raise ValueError(f"classes must be an iterable of class indices, got {classes!r}") from None
+    for c in items:
+        if isinstance(c, bool):
+            raise ValueError(f"classes: {c!r} is not a class index")
+        try:
+            i = operator.index(c)
+        except TypeError:
+            raise ValueError(f"classes: {c!r} is not an integer class index") from None
+        if i < 0 or (num_classes is not None and i >= num_classes):
+            raise ValueError(f"classes: index {i} outside [0, {num_classes if num_classes is not None else 'num_classes'})")
+        out.add(i)
+    return tuple(sorted(out))
 
 
 def dtype_code(dt: torch.dtype) -> int:

@@ -58,6 +58,7 @@ int postprocess_launch(const ymi_post_desc* d, hipStream_t s);
 int post_begin_launch(const ymi_post_desc* d, hipStream_t s);
 int post_finish_launch(const ymi_post_desc* d, hipStream_t s);
 int post_check_batch(const ymi_post_desc* d);
+int post_set_classes_launch(const ymi_post_desc* d, const int32_t* classes, int count, hipStream_t s);
 int conv_head_decode_launch(const ymi_conv_desc* d, const ymi_post_desc* post, int level, hipStream_t s);
 int conv_head_decode_group_launch(const ymi_conv_desc* descs, int n_levels, const ymi_post_desc* post, hipStream_t s);
 
@@ -109,6 +110,9 @@ struct ymi_plan {
     hipEvent_t ev_in = nullptr, ev_conv = nullptr, ev_done = nullptr;
     bool submitted = false;
     std::vector<void*> owned;   // device memory of an imported plan (ymi_plan_import): freed with it
+    // YMI_POST_CLASS_FILTER: the list last given to ymi_plan_set_classes (the masks themselves live in the descriptors' workspaces); travels with an exported plan
+    bool has_classes = false;
+    std::vector<int32_t> classes;
 };
 
 using namespace ymi;
@@ -295,6 +299,40 @@ extern "C" int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d) {
 }
 
 extern "C" int ymi_plan_num_ops(const ymi_plan* p) { return p ? (int)p->ops.size() : 0; }
+
+// the class mask of every post-process descriptor of the plan that carries YMI_POST_CLASS_FILTER (begin / head / finish ops of one post-process share a workspace: written once)
+static int plan_write_classes(const ymi_plan* p, const int32_t* classes, int count, hipStream_t s) {
+    auto filtered = [](const Op& op) {
+        const bool post = op.kind == OP_POST || op.kind == OP_POST_BEGIN || op.kind == OP_HEAD_DECODE || op.kind == OP_HEAD_GROUP || op.kind == OP_POST_FINISH;
+        return post && (op.post.flags & YMI_POST_CLASS_FILTER) != 0;
+    };
+    // the list is checked against EVERY descriptor before the first mask is written: a refused call leaves every workspace as it was
+    for (const Op& op : p->ops) {
+        if (!filtered(op)) continue;
+        for (int i = 0; i < count; ++i)
+            YMI_REQUIRE(classes[i] >= 0 && classes[i] < op.post.num_classes, "ymi_plan_set_classes: class index %d outside [0, %d)", classes[i], op.post.num_classes);
+    }
+    std::vector<const void*> done;
+    for (const Op& op : p->ops) {
+        if (!filtered(op)) continue;
+        bool seen = false;
+        for (const void* w : done) seen = seen || w == op.post.ws;
+        if (seen) continue;
+        if (const int rc = post_set_classes_launch(&op.post, classes, count, s)) return rc;
+        done.push_back(op.post.ws);
+    }
+    YMI_REQUIRE(!done.empty(), "ymi_plan_set_classes: no post-process of the plan carries YMI_POST_CLASS_FILTER");
+    return YMI_OK;
+}
+
+extern "C" int ymi_plan_set_classes(ymi_plan* p, const int32_t* classes, int count, void* stream) {
+    YMI_REQUIRE(p != nullptr, "ymi_plan_set_classes: null plan");
+    YMI_REQUIRE(count >= 0 && (count == 0 || classes != nullptr), "ymi_plan_set_classes: bad class list");
+    if (const int rc = plan_write_classes(p, classes, count, (hipStream_t)stream)) return rc;
+    p->classes.assign(classes, classes + count);
+    p->has_classes = true;
+    return YMI_OK;
+}
 
 extern "C" int ymi_plan_set_fuse_stem(ymi_plan* p, int on) {
     YMI_REQUIRE(p != nullptr, "ymi_plan_set_fuse_stem: null plan");
@@ -494,6 +532,7 @@ struct PlanFileReloc {
     int32_t region;
     int64_t offset;
 };
+static const char CLASSES_MAGIC[9] = "YMICLS01";   // optional trailer behind the ops: int32 count, int32 classes[count]
 }  // namespace ymi
 
 extern "C" int ymi_plan_export(const ymi_plan* p, const ymi_plan_region* regions, int n_regions, const char* path, void* stream) {
@@ -549,6 +588,10 @@ extern "C" int ymi_plan_export(const ymi_plan* p, const ymi_plan_region* regions
         });
         const int32_t nrel = (int32_t)rel.size();
         ok = fwrite(&op, sizeof(op), 1, f) == 1 && fwrite(&nrel, sizeof(nrel), 1, f) == 1 && (nrel == 0 || fwrite(rel.data(), sizeof(PlanFileReloc), rel.size(), f) == rel.size());
+    }
+    if (ok && rc == YMI_OK && p->has_classes) {   // optional trailer: the class list of ymi_plan_set_classes (a plan without one ends after its ops, as before)
+        const int32_t cnt = (int32_t)p->classes.size();
+        ok = fwrite(CLASSES_MAGIC, 8, 1, f) == 1 && fwrite(&cnt, sizeof(cnt), 1, f) == 1 && (cnt == 0 || fwrite(p->classes.data(), sizeof(int32_t), p->classes.size(), f) == p->classes.size());
     }
     ok = (fclose(f) == 0) && ok;
     if (rc != YMI_OK) return rc;
@@ -619,6 +662,19 @@ extern "C" int ymi_plan_import(const char* path, ymi_plan** out_plan, ymi_plan_r
         });
         if (bad || k != rel.size()) return fail("corrupt relocation");
         p->ops.push_back(op);
+    }
+    char tag[8];
+    if (fread(tag, 8, 1, f) == 1) {   // the exporting plan's class list: the masks are written again before anything can run (on the null stream, and waited for
+                                      // here: an import has no stream of the caller's, and like its uploads above it is complete when it returns)
+        int32_t cnt = 0;
+        if (memcmp(tag, CLASSES_MAGIC, 8) != 0 || fread(&cnt, sizeof(cnt), 1, f) != 1 || cnt < 0 || cnt > (1 << 20)) return fail("corrupt class list");
+        std::vector<int32_t> cls((size_t)cnt);
+        if (cnt && fread(cls.data(), sizeof(int32_t), cls.size(), f) != cls.size()) return fail("truncated class list");
+        if (ymi_plan_set_classes(p, cls.data(), cnt, nullptr) != YMI_OK || hipStreamSynchronize(nullptr) != hipSuccess) {
+            fclose(f);
+            ymi_plan_destroy(p);
+            return YMI_EINVAL;   // (the message of ymi_plan_set_classes stands)
+        }
     }
     fclose(f);
     if (n_regions_out) *n_regions_out = h.n_regions;

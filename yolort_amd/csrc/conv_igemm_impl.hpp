@@ -564,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_v2_tp_kernel(const ConvArgs
 // (28 KiB, the size of the decode buffers) leave room for five blocks per CU, which hide more latency than a third stage
 template <int NA> constexpr int hd_stages() { return NA == 3 ? 3 : 2; }
 
-template <int TNA, int NA>
+template <int TNA, int NA, bool FILT>
 struct DecodeEpilogue {
     const ConvArgs& a;
     const HeadDecodeArgs& h;
@@ -575,14 +575,15 @@ struct DecodeEpilogue {
         uint64_t* bhi = reinterpret_cast<uint64_t*>(smem) + wave * HD_BUF;
         uint32_t* blo = reinterpret_cast<uint32_t*>(reinterpret_cast<uint64_t*>(smem) + 4 * HD_BUF) + wave * HD_BUF;
         u32x4* wl = reinterpret_cast<u32x4*>(reinterpret_cast<char*>(smem) + 4 * HD_BUF * 12) + wave * HD_WL;
-        head_decode_wave<TNA, NA>(a, h, acc, mbase + (lane & 31), lane, bhi, blo, wl, NA == 3 ? 0 : cbase0 / (32 * TNA));
+        head_decode_wave<TNA, NA, FILT>(a, h, acc, mbase + (lane & 31), lane, bhi, blo, wl, NA == 3 ? 0 : cbase0 / (32 * TNA));
     }
 };
 
 // NA = 3: one wave per SIMD (400 registers); NA = 1: three blocks per pixel tile, >= 3 waves per SIMD
-template <int DT, int TNA, int NA>
+// FILT: the class filter (YMI_POST_CLASS_FILTER) is compiled into kernels of its own, chosen by the launchers; the others do not know of it
+template <int DT, int TNA, int NA, bool FILT = false>
 __global__ __launch_bounds__(256, NA == 3 ? 1 : 3) void conv_head_decode_kernel(const ConvArgs a, const HeadDecodeArgs h) {
-    conv_igemm_v2_body<DT, YMI_F32, 128, 32 * TNA * NA, 32, 32 * TNA * NA, hd_stages<NA>(), true, false, true>(a, DecodeEpilogue<TNA, NA>{a, h}, blockIdx.x);
+    conv_igemm_v2_body<DT, YMI_F32, 128, 32 * TNA * NA, 32, 32 * TNA * NA, hd_stages<NA>(), true, false, true>(a, DecodeEpilogue<TNA, NA, FILT>{a, h}, blockIdx.x);
 }
 
 // every pyramid level's head in ONE launch: the levels are independent and the coarse ones have few blocks (100 for a
@@ -594,7 +595,7 @@ struct HeadGroupArgs {
     int n;
 };
 
-template <int DT, int TNA, int NA>
+template <int DT, int TNA, int NA, bool FILT = false>
 __global__ __launch_bounds__(256, NA == 3 ? 1 : 3) void conv_head_decode_group_kernel(const HeadGroupArgs g) {
     // The level is a wave-uniform index into the argument block.  Indexing the by-value parameter copies the block to
     // scratch, and copying the selected level's structs with selects cost ~250 SALU per wave; reading the block through the
@@ -609,7 +610,7 @@ __global__ __launch_bounds__(256, NA == 3 ? 1 : 3) void conv_head_decode_group_k
     const ConvArgs& a = gp->a[l];
     const HeadDecodeArgs& h = gp->h[l];
     const int first = gp->first_block[l];
-    conv_igemm_v2_body<DT, YMI_F32, 128, 32 * TNA * NA, 32, 32 * TNA * NA, hd_stages<NA>(), true, false, true>(a, DecodeEpilogue<TNA, NA>{a, h}, (int)blockIdx.x - first);
+    conv_igemm_v2_body<DT, YMI_F32, 128, 32 * TNA * NA, 32, 32 * TNA * NA, hd_stages<NA>(), true, false, true>(a, DecodeEpilogue<TNA, NA, FILT>{a, h}, (int)blockIdx.x - first);
 }
 
 template <typename K>
@@ -756,37 +757,41 @@ inline size_t head_decode_lds(int tna) {
     return lds < need ? need : lds;
 }
 
-// the launchers take the anchor split from ConvArgs::nblk_n (1: a wave holds all three anchors, 3: one anchor per block)
+// the launchers take the anchor split from ConvArgs::nblk_n (1: a wave holds all three anchors, 3: one anchor per block) and the class-filter form from the sink's mask pointer
+template <typename K, typename... Args>
+int launch_head_kernel(K kfn, const char* name, int blocks, size_t lds, hipStream_t s, const Args&... args) {
+    if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)kfn, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
+    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, s, args...);
+    return check_launch(name);
+}
+
 template <int DT, int TNA>
 int launch_head_decode(const ConvArgs& a, const HeadDecodeArgs& h, hipStream_t s) {
+    const char* name = "conv_head_decode_kernel";
+    const bool filt = h.sink.cmask != nullptr;
     if (a.nblk_n == 3) {
         const size_t lds = head_decode_lds<1>(TNA);
-        auto kfn = conv_head_decode_kernel<DT, TNA, 1>;
-        if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)kfn, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
-        hipLaunchKernelGGL(kfn, dim3(a.nblk_m * 3), dim3(256), lds, s, a, h);
-        return check_launch("conv_head_decode_kernel");
+        if (filt) return launch_head_kernel(conv_head_decode_kernel<DT, TNA, 1, true>, name, a.nblk_m * 3, lds, s, a, h);
+        return launch_head_kernel(conv_head_decode_kernel<DT, TNA, 1, false>, name, a.nblk_m * 3, lds, s, a, h);
     }
     const size_t lds = head_decode_lds<3>(TNA);
-    auto kfn = conv_head_decode_kernel<DT, TNA, 3>;
-    if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)kfn, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
-    hipLaunchKernelGGL(kfn, dim3(a.nblk_m), dim3(256), lds, s, a, h);
-    return check_launch("conv_head_decode_kernel");
+    if (filt) return launch_head_kernel(conv_head_decode_kernel<DT, TNA, 3, true>, name, a.nblk_m, lds, s, a, h);
+    return launch_head_kernel(conv_head_decode_kernel<DT, TNA, 3, false>, name, a.nblk_m, lds, s, a, h);
 }
 
 template <int DT, int TNA>
 int launch_head_group(const HeadGroupArgs& g, hipStream_t s) {
+    const char* name = "conv_head_decode_group_kernel";
+    const bool filt = g.h[0].sink.cmask != nullptr;   // one post-process descriptor for every level
+    const int blocks = g.first_block[g.n];
     if (g.a[0].nblk_n == 3) {
         const size_t lds = head_decode_lds<1>(TNA);
-        auto kfn = conv_head_decode_group_kernel<DT, TNA, 1>;
-        if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)kfn, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
-        hipLaunchKernelGGL(kfn, dim3(g.first_block[g.n]), dim3(256), lds, s, g);
-        return check_launch("conv_head_decode_group_kernel");
+        if (filt) return launch_head_kernel(conv_head_decode_group_kernel<DT, TNA, 1, true>, name, blocks, lds, s, g);
+        return launch_head_kernel(conv_head_decode_group_kernel<DT, TNA, 1, false>, name, blocks, lds, s, g);
     }
     const size_t lds = head_decode_lds<3>(TNA);
-    auto kfn = conv_head_decode_group_kernel<DT, TNA, 3>;
-    if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)kfn, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
-    hipLaunchKernelGGL(kfn, dim3(g.first_block[g.n]), dim3(256), lds, s, g);
-    return check_launch("conv_head_decode_group_kernel");
+    if (filt) return launch_head_kernel(conv_head_decode_group_kernel<DT, TNA, 3, true>, name, blocks, lds, s, g);
+    return launch_head_kernel(conv_head_decode_group_kernel<DT, TNA, 3, false>, name, blocks, lds, s, g);
 }
 
 }  // namespace ymi

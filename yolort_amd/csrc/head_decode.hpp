@@ -16,6 +16,8 @@
 //     (The LDS operand ring is dead by then and is reused for both.)
 // In best-class mode (YMI_POST_BEST_CLASS, CandSink::best) the last two steps become: in-register maximum of the anchor's class logits, exact scores of the classes near
 // it, one cross-half exchange, ONE record per passing (pixel, anchor) -- see the branch below.
+// With a class filter (YMI_POST_CLASS_FILTER, CandSink::cmask) rows of disallowed classes are dropped next to the theta pre-filter (multi-label), or the anchor's
+// record is dropped when its best class is not allowed (best-class).  That is a separate instantiation (FILT): the kernels without a filter are the code they were.
 // Records and boxes are bit-identical to decode_kernel's (postprocess.hip), so sort / NMS / top-k are unchanged.
 #pragma once
 #include "conv_common.hpp"
@@ -44,7 +46,9 @@ struct HeadDecodeArgs {
 
 // acc[NA*TNA][1]: sub-tile s of the wave's anchor qi is acc[qi*TNA + s][0] (anchor q = q_base + qi; q_base is wave-uniform,
 // 0 when NA = 3); register g*4+e of lane (px, hi) is channel c = s*32 + g*8 + hi*4 + e of that anchor (c < K real, else padding)
-template <int TNA, int NA>
+// FILT: the class filter is a SEPARATE instantiation (the launchers pick it when CandSink::cmask is set), so the kernels without a filter are the code they were, register for
+// register (profiles/class_filter_head_registers.txt); with FILT, k_.cmask is not null.
+template <int TNA, int NA, bool FILT = false>
 __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDecodeArgs& h, const f32x16 (&acc)[NA * TNA][1], int m, int lane,
                                                  uint64_t* bhi, uint32_t* blo, u32x4* wl, int q_base) {
     constexpr int HD_BUF = HdCfg<NA>::BUF, HD_WL = HdCfg<NA>::WL;
@@ -125,6 +129,26 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
         wl_fill += cnt;
     };
 
+    // Class filter (YMI_POST_CLASS_FILTER, CandSink::cmask; FILT instantiations only).  Register r of a lane holds the same row c = cb + 4 * hi of EVERY anchor, so
+    // the lane's 16 * TNA rows get their verdict once per wave: `rows` has bit r set iff row r is a class row (5 <= c < K) of an allowed class.  The mask words are read
+    // with wave-uniform loads and shifted by the five box / objectness rows into row space (bit c of word c >> 5); a lane then picks the four nibbles of its lane half out
+    // of each sub-tile's word.  Two VGPRs at most, nothing kept in scalar registers across the anchors.
+    uint64_t rows = 0;
+    if constexpr (FILT) {
+        uint32_t prev = 0;
+        static_for<0, TNA>([&](auto st) {
+            constexpr int s = decltype(st)::value;
+            const uint32_t cur = k_.cmask[s];                                   // classes 32 s .. 32 s + 31
+            uint32_t word = (cur << 5) | (s == 0 ? 0u : (prev >> 27));          // rows 32 s .. 32 s + 31
+            prev = cur;
+            const int left = h.K - 32 * s;                                      // rows of this sub-tile below K
+            word = left >= 32 ? word : (left <= 0 ? 0u : (word & ((1u << left) - 1u)));
+            const uint32_t x = word >> (4 * hi);
+            const uint32_t mine = (x & 0xfu) | ((x >> 4) & 0xf0u) | ((x >> 8) & 0xf00u) | ((x >> 12) & 0xf000u);   // bit g * 4 + e = row s * 32 + g * 8 + hi * 4 + e
+            rows |= (uint64_t)mine << (16 * s);
+        });
+    }
+
     // compile-time indices everywhere: the accumulators must stay in registers (a runtime index sends them to scratch)
     static_for<0, NA>([&](auto qt) {
         constexpr int qi = decltype(qt)::value;
@@ -185,7 +209,9 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
             });
             const BestClass t = {__shfl_xor(b.s, 32, 64), __shfl_xor(b.c, 32, 64)};
             if (best_before(t.s, t.c, b)) b = t;
-            append(pass && hi == 0 && b.c != 0x7fffffff && b.s > k_.thr, b.s, lo_base | (unsigned)(b.c - 5), img);   // conf > thr, strict (general.py:583)
+            bool ok = pass && hi == 0 && b.c != 0x7fffffff && b.s > k_.thr;   // conf > thr, strict (general.py:583)
+            if constexpr (FILT) ok = ok && class_allowed(k_.cmask, ok ? b.c - 5 : 0);   // the winner -- over ALL classes -- has to be an allowed one (general.py:585-587)
+            append(ok, b.s, lo_base | (unsigned)(b.c - 5), img);
             return;
         }
         // cls * o > thr  =>  sigmoid(v) > thr / o  =>  v > logit(thr / o); the margin keeps the filter a superset.
@@ -195,12 +221,15 @@ __device__ __forceinline__ void head_decode_wave(const ConvArgs& a, const HeadDe
             const float p = k_.thr / o;
             theta = p > 0.0f ? __logf(p / (1.0f - p)) - 0.02f : -INFINITY;
         }
+        // FILT: rows of disallowed classes never reach the worklist (`rows` also states 5 <= c < K); the objectness skip and theta stay supersets
         static_for<0, TNA * 16>([&](auto rt) {
             constexpr int r = decltype(rt)::value;
             constexpr int s = r / 16, g = (r % 16) / 4, e = r % 4;
             const int c = s * 32 + g * 8 + hi * 4 + e;
             const float v = acc[q * TNA + s][0][g * 4 + e];
-            const bool pre = (c >= 5) && (c < h.K) && (v > theta);
+            bool pre;
+            if constexpr (FILT) pre = ((rows >> r) & 1ull) && (v > theta);
+            else pre = (c >= 5) && (c < h.K) && (v > theta);
             if (__ballot(pre) == 0) return;          // the common case
             push(pre, v, o, lo_base | (unsigned)(c - 5));
         });

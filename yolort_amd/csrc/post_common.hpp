@@ -22,8 +22,13 @@ struct Workspace {
     uint64_t* p_hi;       // per-class order P of the per-image sort path (cand_cap each)
     uint32_t* p_lo;
     int* sel_count;       // (2n) per-image sort path: records kept by the score-prefix selection, then [n..2n) truncated flags
+    uint32_t* cmask;      // (CLASS_MASK_WORDS) YMI_POST_CLASS_FILTER: bit c & 31 of word c >> 5 set = class c is allowed.  Carved LAST (every other offset is where it
+                          // was) and written by ymi_post_set_classes / the consumer only: ymi_post_begin and the reset kernel leave it alone
+    int64_t cmask_off;    // its byte offset within `ws`
     int64_t total;
 };
+
+constexpr int CLASS_MASK_WORDS = 128;   // 4096 classes, the library's limit on num_classes
 
 constexpr int SORT_ITEMS = 2048;  // records per block per radix pass (256 threads x 8)
 
@@ -48,6 +53,8 @@ inline Workspace carve(void* ws, int n, int total_anchors, int cand_cap) {
     w.p_hi = (uint64_t*)take((int64_t)cand_cap * 8);
     w.p_lo = (uint32_t*)take((int64_t)cand_cap * 4);
     w.sel_count = (int*)take((int64_t)(n > 0 ? n : 1) * 8);
+    w.cmask_off = off;
+    w.cmask = (uint32_t*)take((int64_t)CLASS_MASK_WORDS * 4);
     w.total = off;
     return w;
 }
@@ -71,7 +78,10 @@ struct CandSink {
     int label_bits;
     float thr;             // score threshold (strict >)
     int best;              // YMI_POST_BEST_CLASS: one record per anchor (its best class) instead of one per (anchor, class) pair; wave-uniform
+    const uint32_t* cmask; // YMI_POST_CLASS_FILTER: the allowed-class bit set (Workspace::cmask), a record is written only for an allowed class; null = no filter; wave-uniform
 };
+// is class c (0 <= c < 4096) in the set?  One word load at a class-derived index.
+__device__ __forceinline__ bool class_allowed(const uint32_t* cmask, int c) { return (cmask[c >> 5] >> (c & 31)) & 1u; }
 
 // layout decisions shared by every producer / consumer of the records of one ymi_post_desc
 struct PostLayout {
@@ -96,6 +106,7 @@ inline CandSink make_sink(const ymi_post_desc* d, const Workspace& w, const Post
     k.img_count = L.per_image ? w.img_count : nullptr; k.cap_img = L.cap_img;
     k.total_anchors = L.total_anchors; k.label_bits = L.label_bits; k.thr = d->score_thresh;
     k.best = (d->flags & YMI_POST_BEST_CLASS) != 0;
+    k.cmask = (d->flags & YMI_POST_CLASS_FILTER) ? w.cmask : nullptr;
     return k;
 }
 

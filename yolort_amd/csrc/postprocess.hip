@@ -22,13 +22,20 @@
 // Only the candidate producers know the mode (CandSink::best: decode_kernel here, the head epilogue in head_decode.hpp); sort (ties by anchor), class-aware NMS, top-k,
 // rescale, slab and status words are the ones above.  num_classes == 1: bit-identical to the default; thresholds <= 0: every anchor yields its best class.
 // Differences from ultralytics: the NMS is the true class-aware NMS of this file, not boxes offset by 4096 pixels per class; no max_nms = 30000 cut of the candidates;
-// scores stay fp32; `classes=` filtering is not part of it.
+// scores stay fp32.
+//
+// Class filter (YMI_POST_CLASS_FILTER in ymi_post_desc.flags; Python: classes=[...]; ultralytics' non_max_suppression(..., classes=...), yolort/v5/utils/general.py:585-587).
+// The set of allowed classes is a bit set in the workspace (Workspace::cmask, written by ymi_post_set_classes).  Only the candidate producers read it (CandSink::cmask:
+// decode_kernel here, the head epilogue in head_decode.hpp): multi-label mode writes a record for a passing (anchor, class) pair only if the class is allowed; best-class
+// mode takes the best class over ALL classes as before and writes the anchor's record only if that class is allowed.  Sort, NMS (class-aware or agnostic), top-k, rescale,
+// slab and status words see fewer records and are unchanged; status[4] counts what was produced after the filter.
 //
 // Class-agnostic NMS (YMI_POST_AGNOSTIC in ymi_post_desc.flags; Python: agnostic=True; stand-alone: ymi_nms).  Candidates, sort, top-k, rescale, slab, status words and the
 // labels of the kept detections are those above; only the suppression changes: one greedy NMS over all candidates of an image (torchvision.ops.nms on the unshifted boxes,
 // ultralytics' agnostic=True).  The host keys P with label 0 -- P is G's order, a segment is an image -- and nms_block_kernel (section 3b) walks each segment with a workgroup.
 #include "post_common.hpp"
 #include <cstdlib>
+#include <cstring>
 
 namespace ymi {
 
@@ -138,7 +145,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
                     const BestClass t = {__shfl_xor(b.s, d, 64), __shfl_xor(b.c, d, 64)};
                     if (best_before(t.s, t.c, b)) b = t;
                 }
-                if (b.c != 0x7fffffff && b.s > k_.thr) {    // conf > thr, strict (general.py:583)
+                // conf > thr, strict (general.py:583); YMI_POST_CLASS_FILTER: the best class -- taken over ALL classes -- has to be an allowed one (general.py:585-587)
+                if (b.c != 0x7fffffff && b.s > k_.thr && (k_.cmask == nullptr || class_allowed(k_.cmask, b.c))) {
                     if (lane == 0) {
                         const int anchor = a.level_off + (k * a.h + y) * a.w + x;
                         bhi[fill + cnt] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(b.s));
@@ -170,6 +178,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
                     const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
                     s = __fmul_rn(sigmoid_acc(v[e]), o);  // box_head.py:357 scores = cls * obj
                     ok = s > k_.thr;                       // box_head.py:418 strict >
+                    if (k_.cmask != nullptr) ok = ok && class_allowed(k_.cmask, cls);   // YMI_POST_CLASS_FILTER (wave-uniform pointer test)
                 }
                 sc[e] = s;
                 const int anchor = a.level_off + (k * a.h + y) * a.w + x;
@@ -1537,6 +1546,35 @@ int post_begin_launch(const ymi_post_desc* d, hipStream_t s) {
     return check_launch("post_reset_kernel");
 }
 
+// ---- class filter (YMI_POST_CLASS_FILTER): the allowed-class bit set lives in the workspace (Workspace::cmask), so changing the SET needs no new descriptor, no
+// re-record of a plan and no re-capture of a graph.  The words travel BY VALUE as the kernel's argument: the caller's list is dead weight once the call returns, the
+// launch is ordered on `s` like any other and can be captured.
+struct ClassMaskWords { uint32_t w[CLASS_MASK_WORDS]; };
+__global__ __launch_bounds__(CLASS_MASK_WORDS) void class_mask_write_kernel(uint32_t* dst, const ClassMaskWords m) {
+    dst[threadIdx.x] = m.w[threadIdx.x];
+}
+
+int post_set_classes_launch(const ymi_post_desc* d, const int32_t* classes, int count, hipStream_t s) {
+    YMI_REQUIRE(d != nullptr, "ymi_post_set_classes: null descriptor");
+    YMI_REQUIRE((d->flags & YMI_POST_CLASS_FILTER) != 0, "ymi_post_set_classes: the descriptor's flags lack YMI_POST_CLASS_FILTER");
+    YMI_REQUIRE(d->n >= 1 && d->cand_cap >= 1 && d->ws != nullptr, "ymi_post_set_classes: descriptor without a workspace");
+    YMI_REQUIRE(d->num_levels >= 1 && d->num_levels <= YMI_MAX_LEVELS, "ymi_post_set_classes: num_levels %d out of range", d->num_levels);
+    YMI_REQUIRE(d->num_classes >= 1 && d->num_classes <= 32 * CLASS_MASK_WORDS, "ymi_post_set_classes: num_classes %d out of range", d->num_classes);
+    YMI_REQUIRE(count >= 0 && (count == 0 || classes != nullptr), "ymi_post_set_classes: bad class list");
+    ClassMaskWords m;
+    memset(&m, 0, sizeof(m));
+    for (int i = 0; i < count; ++i) {
+        const int c = classes[i];
+        YMI_REQUIRE(c >= 0 && c < d->num_classes, "ymi_post_set_classes: class index %d outside [0, %d)", c, d->num_classes);
+        m.w[c >> 5] |= 1u << (c & 31);
+    }
+    const PostLayout L = post_layout(d);
+    const Workspace w = carve(d->ws, d->n, L.total_anchors, d->cand_cap);
+    YMI_REQUIRE(d->ws_bytes >= w.total, "ymi_post_set_classes: workspace too small (%lld < %lld)", (long long)d->ws_bytes, (long long)w.total);
+    hipLaunchKernelGGL(class_mask_write_kernel, dim3(1), dim3(CLASS_MASK_WORDS), 0, s, w.cmask, m);
+    return check_launch("class_mask_write_kernel");
+}
+
 // stage 2 of 3 (unfused form): decode + threshold of the fp32 head outputs
 static int post_decode_launch(const ymi_post_desc* d, hipStream_t s) {
     PostLayout L;
@@ -1684,6 +1722,12 @@ extern "C" int64_t ymi_postprocess_ws_bytes(int n, int total_anchors, int cand_c
     if (n <= 0 || total_anchors <= 0 || cand_cap <= 0) return 0;
     return carve(nullptr, n, total_anchors, cand_cap).total;
 }
+
+extern "C" int64_t ymi_post_class_mask_offset(int n, int total_anchors, int cand_cap) {
+    if (n <= 0 || total_anchors <= 0 || cand_cap <= 0) return YMI_EINVAL;
+    return carve(nullptr, n, total_anchors, cand_cap).cmask_off;
+}
+extern "C" int ymi_post_set_classes(const ymi_post_desc* d, const int32_t* classes, int count, void* stream) { return post_set_classes_launch(d, classes, count, (hipStream_t)stream); }
 
 extern "C" int ymi_postprocess(const ymi_post_desc* d, void* stream) { return postprocess_launch(d, (hipStream_t)stream); }
 extern "C" int ymi_post_begin(const ymi_post_desc* d, void* stream) { return post_begin_launch(d, (hipStream_t)stream); }

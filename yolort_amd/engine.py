@@ -645,8 +645,11 @@ class Plan:
 
     def post_desc(self, levels: Sequence[Tuple[int, int]], n: int, strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
                   score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: int, rescale: Optional[Tensor] = None,
-                  logits: Optional[Sequence[View]] = None, flags: int = 0) -> Tuple["PostBuffers", PostDesc]:
-        """descriptor + output slab + workspace of one post-process; `levels` = [(h, w)] per pyramid level"""
+                  logits: Optional[Sequence[View]] = None, flags: int = 0, classes: Optional[Sequence[int]] = None) -> Tuple["PostBuffers", PostDesc]:
+        """descriptor + output slab + workspace of one post-process; `levels` = [(h, w)] per pyramid level.  `classes` (not None): the allowed class set -- sets
+        YMI_POST_CLASS_FILTER and writes the workspace's mask on the current stream; PostBuffers.set_classes changes the set later"""
+        if classes is not None:
+            flags |= _lib.POST_CLASS_FILTER
         total_anchors = sum(3 * h * w for h, w in levels)
         pb = PostBuffers(self, n, detections_per_img, total_anchors, cand_cap, rescale)
         d = PostDesc()
@@ -669,15 +672,18 @@ class Plan:
         d.ws, d.ws_bytes, d.cand_cap = pb.ws.data_ptr(), pb.ws.numel(), cand_cap
         d.flags = flags
         pb.total_anchors = total_anchors
+        pb.desc = d
         self.keep.extend([pb, d])
+        if classes is not None:
+            pb.set_classes(classes)
         return pb, d
 
     def postprocess(self, logits: Sequence[View], strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
                     score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: int, rescale: Optional[Tensor] = None,
-                    flags: int = 0) -> "PostBuffers":
+                    flags: int = 0, classes: Optional[Sequence[int]] = None) -> "PostBuffers":
         """decode of stored fp32 logits + sort + NMS + top-k as ONE op (the unfused form)"""
         pb, d = self.post_desc([(v.h, v.w) for v in logits], logits[0].n, strides, anchors, num_classes, score_thresh, nms_thresh, detections_per_img,
-                               cand_cap, rescale, logits=logits, flags=flags)
+                               cand_cap, rescale, logits=logits, flags=flags, classes=classes)
         self._record(self.lib.ymi_plan_add_postprocess(self.handle, C.byref(d)), "postprocess", kind="post", flops=0.0,
                      bytes=float(sum(v.n * v.h * v.w * 3 * (num_classes + 5) * 4 for v in logits)), shape=f"A={pb.total_anchors}")
         return pb
@@ -797,6 +803,14 @@ class Plan:
                     walk(v)
 
         walk(self.keep)
+        # The plan file carries the class list of a filtered post-process (the importer writes the mask again).  ymi_plan_set_classes is how the plan learns the list, so
+        # exporting also LAUNCHES a write of that same list into the workspace's mask on the current stream: harmless (the mask already holds it), but a launch.
+        for o in self.keep:
+            if isinstance(o, PostBuffers) and int(o.desc.flags) & _lib.POST_CLASS_FILTER:
+                if o.classes is None:
+                    raise YmiError("Plan.export: the post-process has YMI_POST_CLASS_FILTER but its class set was never written (PostBuffers.set_classes)")
+                arr = (C.c_int32 * max(1, len(o.classes)))(*o.classes)
+                check(self.lib.ymi_plan_set_classes(self.handle, arr, len(o.classes), _lib.stream_ptr()), "ymi_plan_set_classes")
         add(self.zeros, REGION_SCRATCH)
         const_ids = getattr(self, "_const_tensors", set())
         tags = {int(t.untyped_storage().data_ptr()): tag for tag, t in (io or {}).items()}
@@ -850,3 +864,17 @@ class PostBuffers:
         nbytes = plan.lib.ymi_postprocess_ws_bytes(n, total_anchors, cand_cap)
         self.ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         plan.bytes_allocated += nbytes
+        self.lib = plan.lib
+        self.desc: Optional[PostDesc] = None       # set by Plan.post_desc
+        self.classes: Optional[Tuple[int, ...]] = None   # the set the workspace's class mask holds (None: never written)
+
+    def set_classes(self, classes: Sequence[int], stream: Optional[torch.cuda.Stream] = None) -> None:
+        """YMI_POST_CLASS_FILTER: writes the allowed class set into the workspace's mask on `stream` (default: the current one), ordered like any launch -- batches
+        enqueued behind it on that stream (or on streams that wait for it) are filtered by the new set; no plan is re-recorded, no graph re-captured.  ValueError for an
+        index outside [0, num_classes); YmiError when the descriptor was built without the flag."""
+        if classes is None:
+            raise ValueError("set_classes: a class set is needed (no filter is a descriptor without YMI_POST_CLASS_FILTER)")
+        cls = _lib.normalize_classes(classes, int(self.desc.num_classes))
+        arr = (C.c_int32 * max(1, len(cls)))(*cls)
+        check(self.lib.ymi_post_set_classes(C.byref(self.desc), arr, len(cls), _lib.stream_ptr(stream)), "ymi_post_set_classes")
+        self.classes = cls

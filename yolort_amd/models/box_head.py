@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -109,16 +109,31 @@ class PostProcess(nn.Module):
     pair above the threshold is a candidate (box_head.py:418); False is the contract of ultralytics' non_max_suppression(..., multi_label=False)
     (yolort/v5/utils/general.py:572-583, what AutoShape uses): an anchor yields at most one detection, its class with the largest cls * obj (the lowest index among
     equal products).  An attribute of a live model: flipping it takes effect on the next batch.  `agnostic` (default False; ultralytics' agnostic=True): one NMS over all
-    boxes of an image, whatever their label -- torchvision.ops.nms on the unshifted boxes; labels of the kept detections are unchanged.  Also a live attribute."""
+    boxes of an image, whatever their label -- torchvision.ops.nms on the unshifted boxes; labels of the kept detections are unchanged.  Also a live attribute.
+    `classes` (an attribute, None = no filter; ultralytics' classes=[...], yolort/v5/utils/general.py:585-587): the set of allowed class indices, applied where candidates are
+    born -- before NMS and top-k, so no slot of `detections_per_img` goes to an unwanted class and, with `agnostic`, no unwanted box suppresses a wanted one.  With
+    multi_label=False the best class is still taken over all classes, and an anchor whose best class is not allowed yields nothing.  `[]` gives no detections.  A live
+    attribute too: a new SET takes effect on the next batch without a new plan (the set is data in the plan's workspace); only None <-> a set selects another plan.
+    ValueError for a non-integer or negative index here, for an index >= num_classes at the next batch (or at the model's construction)."""
 
     def __init__(self, strides: List[int], score_thresh: float, nms_thresh: float, detections_per_img: int, multi_label: bool = True, agnostic: bool = False) -> None:
         super().__init__()
         self.multi_label = multi_label
         self.agnostic = agnostic
+        self.classes = None   # (the constructor's parameter list is the one it was: YOLO(...), the factories and YOLOv5(...) take `classes=` and set it here)
         self.strides = strides
         self.score_thresh = score_thresh
         self.nms_thresh = nms_thresh
         self.detections_per_img = detections_per_img
+
+    @property
+    def classes(self) -> Optional[Tuple[int, ...]]:
+        return self._classes
+
+    @classes.setter
+    def classes(self, value: Optional[Sequence[int]]) -> None:
+        from .._lib import normalize_classes
+        self._classes = normalize_classes(value)   # a sorted tuple without duplicates, or None
 
     def forward(self, head_outputs: List[Tensor], grids: List[Tensor], shifts: List[Tensor]) -> List[Dict[str, Tensor]]:
         """Stand-alone use with the reference calling convention: head_outputs[l] is (N,A,H,W,K);
@@ -131,4 +146,4 @@ class PostProcess(nn.Module):
             anchors.append(a)
         k = head_outputs[0].shape[-1]
         return postprocess_logits(head_outputs, [float(s) for s in self.strides], anchors, k - 5, self.score_thresh, self.nms_thresh, self.detections_per_img,
-                                  multi_label=self.multi_label, agnostic=self.agnostic)
+                                  multi_label=self.multi_label, agnostic=self.agnostic, classes=self.classes)

@@ -9,12 +9,12 @@ Constructor injection points (yolo.py:65-81) are honoured: custom `head`, `ancho
 from __future__ import annotations
 
 import os
-from typing import Any, Callable, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
 
-from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_EXACT_FULL, YmiError, check
+from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_CLASS_FILTER, POST_EXACT_FULL, YmiError, check, normalize_classes
 from ..engine import Plan, View
 from ..hipmodule import compute_dtype_of, nchw_to_view, view_to_nchw, weights_signature
 from ..ops import slab_to_list
@@ -35,6 +35,9 @@ _SKIP_POST = os.environ.get("YOLORT_AMD_DEBUG_SKIP_POST", "0") == "1"   # tuning
 
 DEFAULT_ANCHORS = [[10, 13, 16, 30, 33, 23], [30, 61, 62, 45, 59, 119], [116, 90, 156, 198, 373, 326]]  # yolo.py:94-99
 P6_ANCHORS = [[19, 27, 44, 40, 38, 94], [96, 68, 86, 152, 180, 137], [140, 301, 303, 264, 238, 542], [436, 615, 739, 380, 925, 792]]  # yolo.py:642-647
+
+
+_LIVE = object()   # default of every `classes` parameter below: "post_process.classes as it is now"; a redo passes the set its batch was submitted under instead
 
 
 class _PlanDone:
@@ -65,6 +68,7 @@ class _PlanEntry:
         self.rescale_host = torch.zeros(n, 3, dtype=torch.float32).pin_memory() if post is not None else None
         self.result_host = torch.zeros(8 + n, dtype=torch.int32).pin_memory() if post is not None else None
         self.rescale_set = False
+        self.mask_classes = None   # YMI_POST_CLASS_FILTER: the class set this instance's workspace mask holds (None: not written yet -- a fresh workspace has no valid mask)
         self.rescale_rows = None   # the rows last uploaded to `rescale` (a serving loop sends the same geometry again and again: uploaded once)
         self.done = None        # event recorded after the post-process + result copy of the last submit
         self.outstanding = None  # the PendingDetections of the last submit while the host has not collected it yet
@@ -88,7 +92,7 @@ class PendingDetections:
     """Handle of an in-flight batch (YOLO.submit / YOLOv5.forward_async); `.result()` blocks on its
     completion event only -- later batches keep running on the GPU meanwhile."""
 
-    def __init__(self, owner: "YOLO", entry: _PlanEntry, rows, hook_result=None, planar=None):
+    def __init__(self, owner: "YOLO", entry: _PlanEntry, rows, hook_result=None, planar=None, classes=None):
         self.owner, self.entry, self.rows, self.hook_result = owner, entry, rows, hook_result
         self.event = entry.done
         self._result: Optional[List[Dict[str, Tensor]]] = None
@@ -97,6 +101,8 @@ class PendingDetections:
         self.second_round = False    # gathered(): a stale shard made every rank exchange this batch again
         # planar input images when the stem read them directly (entry.x was never filled): a redo must start from them
         self.planar = planar
+        # the class set this batch was submitted under (YMI_POST_CLASS_FILTER; None = no filter): a redo runs under it again, whatever post_process.classes has become since
+        self.classes = classes
 
     def result(self) -> List[Dict[str, Tensor]]:
         """blocks until this batch is done and returns its List[Dict]; idempotent (the first call detaches the results
@@ -145,13 +151,13 @@ class PendingDetections:
         if host[1] & 2 and not host[1] & 1:   # the score prefix of a crowded image gave < detections_per_img survivors: exact full pass
             if os.environ.get("YOLORT_AMD_VERBOSE"):
                 print("[yolort_amd] score-prefix selection fell short: re-running with the full candidate set", flush=True)
-            return self.owner._redo_exact_full(e, self.rows, self.planar)
+            return self.owner._redo_exact_full(e, self.rows, self.planar, self.classes)
         if host[1] != 0:   # candidate capacity exceeded (nothing truncated): grow, rebuild, redo synchronously
             n = e.x.n
             per_image = host[3] if host[3] > 0 else (host[0] + n - 1) // n   # status[3]: largest per-image count (per-image sort path)
             if os.environ.get("YOLORT_AMD_VERBOSE"):
                 print(f"[yolort_amd] candidate capacity {self.owner.cand_cap_per_image}/image exceeded (status {host[:4]}): growing", flush=True)
-            return self.owner._redo_with_capacity(e, self.rows, per_image, self.planar)
+            return self.owner._redo_with_capacity(e, self.rows, per_image, self.planar, self.classes)
         p = e.post
         return slab_to_list(p.boxes.clone(), p.scores.clone(), p.labels.clone(), host[8:])
 
@@ -172,6 +178,7 @@ class YOLO(nn.Module):
         post_process: Optional[nn.Module] = None,
         multi_label: bool = True,
         agnostic: bool = False,
+        classes: Optional[Sequence[int]] = None,
     ):
         super().__init__()
         if not hasattr(backbone, "out_channels"):
@@ -187,6 +194,10 @@ class YOLO(nn.Module):
         self.num_classes = num_classes
         self.head = head if head is not None else YOLOHead(backbone.out_channels, self.anchor_generator.num_anchors, self.anchor_generator.strides, num_classes)
         self.post_process = post_process if post_process is not None else PostProcess(self.anchor_generator.strides, score_thresh, nms_thresh, detections_per_img, multi_label=multi_label, agnostic=agnostic)
+        if post_process is None:
+            self.post_process.classes = normalize_classes(classes, num_classes)
+        elif classes is not None:   # an injected module is taken as it is: a set given next to it would be dropped without a word
+            raise ValueError("classes= configures the package's own PostProcess: with an injected post_process, set the filter on that module")
         self.compute_dtype = torch.float16  # used when parameters are fp32 (see hipmodule.compute_dtype_of)
         # the conv stack of a batch is replayed as ONE captured hipGraph launch (csrc/api.cpp ymi_plan_run: captured once per plan instance and op range) instead of ~45
         # kernel launches from the host: same kernels, same order, same results (tests/test_boundary_gpu.py), 0.12 ms less host time per batch (profiles/r04n_pipeline_depth_graph.txt).
@@ -259,20 +270,37 @@ class YOLO(nn.Module):
             raise YmiError("export_plan needs the fused post-process (head, anchor generator and post-process of this package)")
         io = {TAG_INPUT: e.x.base, TAG_RESCALE: e.rescale, TAG_BOXES: e.post.boxes, TAG_SCORES: e.post.scores, TAG_LABELS: e.post.labels,
               TAG_STATUS_COUNT: e.post.status_count, TAG_SLAB: e.post.slab}
-        nreg = e.plan.export(path, io)
+        classes = getattr(self.post_process, "classes", None)
+        with torch.cuda.device(device), torch.cuda.stream(e.main_stream):
+            if classes is not None:
+                # the file carries the set the model has NOW: this instance may never have run (its mask unwritten) or have last run under another set.  Written on
+                # the instance's own stream, where its next batch is ordered behind it (the instance is free: _entry hands out drained ones).
+                e.post.set_classes(classes)
+                e.mask_classes = classes
+            nreg = e.plan.export(path, io)
         return {"path": path, "regions": nreg, "ops": e.plan.num_ops, "n_conv_ops": e.n_backbone_ops if hasattr(e, "n_backbone_ops") else None,
                 "input": {"shape": (n, h, w, 4), "dtype": str(e.x.dtype)}, "detections_per_img": int(e.post.k)}
 
     def fused(self) -> bool:
         return type(self.head) is YOLOHead and type(self.post_process) is PostProcess and type(self.anchor_generator) is AnchorGenerator and hasattr(self.backbone, "emit")
 
-    def _post_key(self) -> Optional[Tuple]:
-        """the post-process settings a recorded plan has baked in (part of the plan key, fused and unfused head alike): changing one of them on a live model -- the
-        modes `multi_label` and `agnostic` included -- must not meet a plan recorded for the old value"""
-        pp = self.post_process
-        return (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True)), bool(getattr(pp, "agnostic", False))) if self.fused() else None
+    def _classes(self, classes=_LIVE):
+        return getattr(self.post_process, "classes", None) if classes is _LIVE else classes
 
-    def _entry(self, n: int, h: int, w: int, device: torch.device) -> _PlanEntry:
+    def _post_key(self, classes=_LIVE) -> Optional[Tuple]:
+        """the post-process settings a recorded plan has baked in (part of the plan key, fused and unfused head alike): changing one of them on a live model -- the
+        modes `multi_label` and `agnostic` included -- must not meet a plan recorded for the old value.  Of `classes` only WHETHER there is a filter is baked in
+        (YMI_POST_CLASS_FILTER); the set itself is data in the plan's workspace, rewritten by _submit_entry when it changes"""
+        pp = self.post_process
+        if not self.fused():
+            return None
+        classes = self._classes(classes)
+        if classes and classes[-1] >= self.num_classes:   # (sorted: the largest index last)
+            raise ValueError(f"post_process.classes: index {classes[-1]} outside [0, {self.num_classes})")
+        key = (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True)), bool(getattr(pp, "agnostic", False)))
+        return key if classes is None else key + (True,)   # (the key of a model without a filter is the one it always was)
+
+    def _entry(self, n: int, h: int, w: int, device: torch.device, classes=_LIVE) -> _PlanEntry:
         """a plan instance of this shape whose previous batch has been collected by the host.  Instances are built lazily
         (one at first use, another only when a batch is submitted while every existing one is still in flight, up to
         `pipeline_depth`); when all are busy the oldest is recycled after its uncollected results have been moved into
@@ -281,7 +309,7 @@ class YOLO(nn.Module):
         canvases without rebuilding plans."""
         cdt = compute_dtype_of(self)
         pp = self.post_process
-        post_key = self._post_key()
+        post_key = self._post_key(classes)
 
         base = (n, h, w, cdt, device.index, self._frozen_signature if self._frozen_signature is not None else weights_signature(self), post_key)   # (walks every parameter: once per submission, the host side of a step is ~0.3 ms)
 
@@ -318,7 +346,7 @@ class YOLO(nn.Module):
                 break
         if e is None and len(ring) < max(1, self.pipeline_depth):
             self._evict(key)
-            e = self._build_entry(n, h, w, device, cdt, pp)
+            e = self._build_entry(n, h, w, device, cdt, pp, classes)
             ring.append(e)
         if e is None:       # all busy (their batches are collected but the GPU work of a later use has not drained): recycle the oldest
             e = ring.pop(0)
@@ -339,7 +367,7 @@ class YOLO(nn.Module):
                 if en.outstanding is not None:
                     en.outstanding.result()
 
-    def _build_entry(self, n: int, h: int, w: int, device: torch.device, cdt, pp) -> _PlanEntry:
+    def _build_entry(self, n: int, h: int, w: int, device: torch.device, cdt, pp, classes=_LIVE) -> _PlanEntry:
         plan = Plan(device, cdt)
         x = plan.alloc(n, h, w, 4, zero=True)
         feats = self.backbone.emit(plan, x)
@@ -351,7 +379,7 @@ class YOLO(nn.Module):
             ag = self.anchor_generator
             strides = [float(s) for s in ag.strides]
             args = (self.num_classes, float(pp.score_thresh), float(pp.nms_thresh), int(pp.detections_per_img), self.cand_cap_per_image * n)
-            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0)   # rebuilt plans (capacity growth, exact full pass) come through here too
+            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0) | (POST_CLASS_FILTER if self._classes(classes) is not None else 0)   # rebuilt plans (capacity growth, exact full pass) come through here too
             if self.fuse_head_decode and self.head.can_fuse_decode(plan, feats):
                 post, pd = plan.post_desc([(f.h, f.w) for f in feats], n, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
                 plan.post_begin(pd)
@@ -362,7 +390,7 @@ class YOLO(nn.Module):
                 post = plan.postprocess(logits, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
         return _PlanEntry(plan, x, feats, logits, post, rescale, n_backbone)
 
-    def _submit_entry(self, e: _PlanEntry, rescale_rows: Optional[List[Tuple[float, float, float]]], first_op: int = 0, ev0=None, planar=None, main=None) -> PendingDetections:
+    def _submit_entry(self, e: _PlanEntry, rescale_rows: Optional[List[Tuple[float, float, float]]], first_op: int = 0, ev0=None, planar=None, main=None, classes=_LIVE) -> PendingDetections:
         """input view already filled on the current stream; enqueues the plan and returns a handle.
         Conv stack on the current stream, post-process + result copy on the entry's side stream, so
         the next batch's convolutions overlap this batch's sort/NMS (few, long-running waves)."""
@@ -383,13 +411,19 @@ class YOLO(nn.Module):
             with torch.cuda.stream(main):
                 e.rescale.copy_(e.rescale_host, non_blocking=True)
             e.rescale_rows, e.rescale_set = rescale_rows, True
+        classes = self._classes(classes)
+        if classes is not None and e.mask_classes != classes:
+            # the class set changed (or this instance is new: capacity growth, exact full pass and new shapes come with a fresh workspace): rewrite the mask on the main
+            # stream IN FRONT of the conv range -- the fused head reads it inside that range, and the side stream waits for the range.  Same plan, same captured graphs.
+            e.post.set_classes(classes, stream=main)
+            e.mask_classes = classes
         br = self.bracket
         gather = self._gather_on and not self._in_redo
         if e.c_submit and br is None and not gather and not _SKIP_POST:
             check(e.plan.lib.ymi_plan_submit(e.plan.handle, first_op, e.n_conv_ops, (3 if self.post_graph else 1) if self.use_graph else 0, main.cuda_stream, e.side_ptr, e.post.status_count.data_ptr(),
                                              e.result_host.data_ptr(), e.result_bytes, 1 if self.pipeline_depth <= 1 else 0), "ymi_plan_submit")
             e.done = e.c_done
-            pd = PendingDetections(self, e, rescale_rows, planar=planar)
+            pd = PendingDetections(self, e, rescale_rows, planar=planar, classes=classes)
             e.outstanding = pd
             return pd
         if br is not None:
@@ -432,7 +466,7 @@ class YOLO(nn.Module):
         e.done.record(side)
         if self.pipeline_depth <= 1:
             main.wait_event(e.done)
-        pd = PendingDetections(self, e, rescale_rows, planar=planar)
+        pd = PendingDetections(self, e, rescale_rows, planar=planar, classes=classes)
         pd.gather_issued = gather
         if gather:   # gathered() may hold a collective (second round): it has to be taken batch by batch, in submission order, on every rank
             pd.gather_seq = self._gather_submitted = getattr(self, "_gather_submitted", 0) + 1
@@ -454,30 +488,32 @@ class YOLO(nn.Module):
             e.main_stream.wait_event(e.done)
         return e
 
-    def _resubmit(self, e_old: _PlanEntry, rescale_rows, planar) -> List[Dict[str, Tensor]]:
+    def _resubmit(self, e_old: _PlanEntry, rescale_rows, planar, classes=_LIVE) -> List[Dict[str, Tensor]]:
         """re-run a batch synchronously on a (re)built plan instance: from the planar images when the stem read those
-        directly (the NHWC4 buffer of the old entry was never filled then), else from the old entry's input buffer"""
+        directly (the NHWC4 buffer of the old entry was never filled then), else from the old entry's input buffer.
+        `classes`: the class set the batch was SUBMITTED under (PendingDetections.classes) -- the plan is chosen and the mask written for that set, whatever
+        post_process.classes has become meanwhile; the live attribute is neither read nor touched."""
         x_old = e_old.x
         torch.cuda.synchronize(x_old.base.device)
-        e2 = self._entry(x_old.n, x_old.h, x_old.w, x_old.base.device)
+        e2 = self._entry(x_old.n, x_old.h, x_old.w, x_old.base.device, classes)
         self._in_redo = True   # a local re-run must not issue a collective the other ranks do not (PendingDetections.gathered raises)
         try:
-            return self._resubmit_on(e_old, e2, rescale_rows, planar)
+            return self._resubmit_on(e_old, e2, rescale_rows, planar, classes)
         finally:
             self._in_redo = False
 
-    def _resubmit_on(self, e_old: _PlanEntry, e2: _PlanEntry, rescale_rows, planar) -> List[Dict[str, Tensor]]:
+    def _resubmit_on(self, e_old: _PlanEntry, e2: _PlanEntry, rescale_rows, planar, classes=_LIVE) -> List[Dict[str, Tensor]]:
         x_old = e_old.x
         with torch.cuda.device(x_old.base.device), torch.cuda.stream(e2.main_stream):
             if planar is not None and e2.plan.stem_planar_ok(planar, (x_old.h, x_old.w)):
                 first_op = e2.plan.stem_from_planar(planar)
-                return self._submit_entry(e2, rescale_rows, first_op, planar=planar).result()
+                return self._submit_entry(e2, rescale_rows, first_op, planar=planar, classes=classes).result()
             if planar is not None:
                 raise YmiError("internal: a planar-stem batch cannot be re-run on a plan without the planar stem")
             e2.x.base.copy_(x_old.base)
-            return self._submit_entry(e2, rescale_rows).result()
+            return self._submit_entry(e2, rescale_rows, classes=classes).result()
 
-    def _redo_with_capacity(self, e: _PlanEntry, rescale_rows, needed_per_image: int, planar=None) -> List[Dict[str, Tensor]]:
+    def _redo_with_capacity(self, e: _PlanEntry, rescale_rows, needed_per_image: int, planar=None, classes=_LIVE) -> List[Dict[str, Tensor]]:
         # per-image regions are powers of two (the kernel rounds the capacity DOWN to one): grow to the next power
         # of two that holds the largest image.  Batches submitted before an earlier growth land here too and
         # simply re-run on the already grown plan.
@@ -485,11 +521,11 @@ class YOLO(nn.Module):
         if needed_per_image > cap_eff or e.post.cand_cap >= self.cand_cap_per_image * e.x.n:
             want = max(int(needed_per_image * 1.25) + 1024, 2 * cap_eff)
             self.cand_cap_per_image = 1 << (want - 1).bit_length()
-        return self._resubmit(e, rescale_rows, planar)
+        return self._resubmit(e, rescale_rows, planar, classes)
 
-    def _redo_exact_full(self, e: _PlanEntry, rescale_rows, planar=None) -> List[Dict[str, Tensor]]:
+    def _redo_exact_full(self, e: _PlanEntry, rescale_rows, planar=None, classes=_LIVE) -> List[Dict[str, Tensor]]:
         self.post_exact_full = True
-        return self._resubmit(e, rescale_rows, planar)
+        return self._resubmit(e, rescale_rows, planar, classes)
 
     def _run_entry(self, e: _PlanEntry, rescale_rows: Optional[List[Tuple[float, float, float]]]) -> List[Dict[str, Tensor]]:
         return self._submit_entry(e, rescale_rows).result()
@@ -521,7 +557,7 @@ class YOLO(nn.Module):
 
     @classmethod
     def load_from_yolov5(cls, checkpoint_path: str, score_thresh: float = 0.25, nms_thresh: float = 0.45, version: str = "r6.0",
-                         post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False):
+                         post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False, classes: Optional[Sequence[int]] = None):
         """Load model state from a checkpoint trained by ultralytics/yolov5 (reference yolo.py:185-223)."""
         from ._checkpoint import load_from_ultralytics
 
@@ -529,7 +565,7 @@ class YOLO(nn.Module):
         backbone_name = f"darknet_{info['size']}_{version.replace('.', '_')}"
         backbone = darknet_pan_backbone(backbone_name, info["depth_multiple"], info["width_multiple"], version=version, use_p6=info["use_p6"])
         model = cls(backbone, info["num_classes"], strides=info["strides"], anchor_grids=info["anchor_grids"], score_thresh=score_thresh,
-                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic)
+                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic, classes=classes)
         model.load_state_dict(info["state_dict"])
         return model
 

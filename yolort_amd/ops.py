@@ -71,9 +71,12 @@ def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence
 
 
 def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
-                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True, agnostic: bool = False) -> List[Dict[str, Tensor]]:
+                       score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True, agnostic: bool = False,
+                       classes: Optional[Sequence[int]] = None) -> List[Dict[str, Tensor]]:
     """Runs the fused post-process on reference-layout head outputs [(N,A,H,W,K)] (A == 3).  multi_label=False: one label per anchor, its best class
-    (include/yolort_amd.h YMI_POST_BEST_CLASS).  agnostic=True: one NMS over all boxes of an image, whatever their label (YMI_POST_AGNOSTIC)."""
+    (include/yolort_amd.h YMI_POST_BEST_CLASS).  agnostic=True: one NMS over all boxes of an image, whatever their label (YMI_POST_AGNOSTIC).  classes=[...]: only candidates of these classes, filtered
+    before NMS and top-k (YMI_POST_CLASS_FILTER; multi_label=False: an anchor whose best class is not in the set yields nothing); None = no filter."""
+    classes = _lib.normalize_classes(classes, num_classes)
     _lib.load(require_gpu=True)
     h0 = head_outputs[0]
     if not h0.is_cuda:
@@ -93,7 +96,7 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
     while True:
         plan = Plan(h0.device, torch.float16)
         views = [View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * k, t.shape[3]) for t in plan_inputs]
-        pb = plan.postprocess(views, strides, anchors, num_classes, score_thresh, nms_thresh, detections_per_img, cap, flags=flags)
+        pb = plan.postprocess(views, strides, anchors, num_classes, score_thresh, nms_thresh, detections_per_img, cap, flags=flags, classes=classes)
         plan.run()
         st = pb.status.cpu().tolist()
         if st[1] == 0:
