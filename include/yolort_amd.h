@@ -314,6 +314,32 @@ typedef struct ymi_post_desc {
  * passing anchors whose best class is allowed); the capacity and score-prefix protocols apply to the filtered records.  Honoured wherever YMI_POST_BEST_CLASS is:
  * ymi_postprocess, ymi_conv_head_decode, ymi_conv_head_decode_group, their ymi_plan_add_* forms and the replay of an exported plan. */
 #define YMI_POST_CLASS_FILTER 8
+/* Merge-NMS: every kept box becomes the score-weighted mean of the candidates it overlaps -- ultralytics' non_max_suppression with its local `merge = True`
+ * (yolort/v5/utils/general.py:604-613).  Combines with YMI_POST_EXACT_FULL, YMI_POST_BEST_CLASS, YMI_POST_AGNOSTIC and YMI_POST_CLASS_FILTER.  Candidates, sort
+ * and suppression (class-aware, or agnostic under YMI_POST_AGNOSTIC) are unchanged; per image, after the NMS:
+ *   1. n = the image's candidate count (what the producers emitted for it after threshold, best-class mode and class filter).  The image is merged iff
+ *      1 < n < YMI_MERGE_MAX_N (general.py:606); every other image comes out exactly as without the flag, bit for bit.  The score-prefix selection never cuts an
+ *      image below 4096 records, so a merged image is never a truncated one and YMI_STATUS_PREFIX_SHORT keeps its protocol.
+ *   2. The kept list is the first detections_per_img kept records in rank order, taken BEFORE the merge (general.py:604-605).
+ *   3. The contributors of a kept record i are ALL candidates j of the image, kept or suppressed, i included, that carry its label (any label under
+ *      YMI_POST_AGNOSTIC) and whose fp32 IoU with i is > nms_thresh (strict; the suppression's own expression, NaN never passes); m_i is their number.
+ *   4. merged box = sum_j(score_j * box_j) / sum_j(score_j) per coordinate, in fp32 with every product, sum and the division rounded on its own (no fused
+ *      multiply-add) over the unrescaled decoded boxes; the summation order is a fixed function of the candidates' ranks, so the result is the same on every
+ *      run.  If the weight sum is not > 0 (all-zero scores under a non-positive score_thresh) the box keeps its NMS coordinates.  Score and label are unchanged.
+ *   5. Without YMI_POST_MERGE_KEEP_SINGLE a kept record with m_i <= 1 -- a box nothing else agrees with, or a zero-area box whose IoU with itself is NaN -- is
+ *      dropped (general.py:612-613, `redundant = True`); the survivors are compacted in rank order, slots are NOT refilled: out_count can be below
+ *      detections_per_img although more boxes were kept, as in the reference.  With YMI_POST_MERGE_KEEP_SINGLE nothing is dropped.
+ *   6. rescale ((b - pad) / gain) applies to the merged box; slab, zeroing past the count, YMI_SLAB_STALE and every status word are those of the default
+ *      (status[4] still counts raw candidates).
+ * YMI_POST_MERGE_KEEP_SINGLE is valid only together with YMI_POST_MERGE (alone: YMI_EINVAL).  One workgroup per image (merge_gather_kernel, csrc/postprocess.hip,
+ * launched instead of the top-k gather; without the flag the launch sequence is unchanged).  Honoured wherever YMI_POST_AGNOSTIC is: ymi_postprocess,
+ * ymi_post_finish (the fused head's begin / finish), the ymi_plan_add_* forms, the post-process graph and the replay of an exported plan; ymi_batched_nms and ymi_nms
+ * return indices and are not affected.
+ * Differences from ultralytics: the overlap test runs on the unshifted boxes of the same class, not on boxes offset by 4096 x class; there is no max_nms cut of
+ * the candidates; a non-positive weight sum leaves the box as it is where the reference would emit NaN. */
+#define YMI_POST_MERGE 16
+#define YMI_POST_MERGE_KEEP_SINGLE 32
+#define YMI_MERGE_MAX_N 3000 /* an image is merged iff 1 < candidates < YMI_MERGE_MAX_N */
 #define YMI_STATUS_OVERFLOW_CAPACITY 1 /* status[1] bit 0: candidate capacity exceeded (grow cand_cap) */
 #define YMI_STATUS_PREFIX_SHORT 2      /* status[1] bit 1: prefix too short, re-run with YMI_POST_EXACT_FULL */
 

@@ -66,6 +66,13 @@ POST_EXACT_FULL = 1
 POST_BEST_CLASS = 2   # YMI_POST_BEST_CLASS: one label per anchor (ultralytics' multi_label=False)
 POST_AGNOSTIC = 4     # YMI_POST_AGNOSTIC: one NMS over all boxes of an image, whatever their label (ultralytics' agnostic=True)
 POST_CLASS_FILTER = 8  # YMI_POST_CLASS_FILTER: only candidates of the classes in the workspace's mask (ultralytics' classes=[...])
+POST_MERGE = 16        # YMI_POST_MERGE: merge-NMS, a kept box becomes the score-weighted mean of the candidates it overlaps (ultralytics' merge = True); images of 1 < n < 3000 candidates
+POST_MERGE_KEEP_SINGLE = 32   # YMI_POST_MERGE_KEEP_SINGLE (with POST_MERGE only): keep the boxes that have no contributor but themselves (ultralytics' redundant = False)
+
+
+def merge_flags(merge: bool, merge_redundant: bool = True) -> int:
+    """the YMI_POST_MERGE* bits of `merge=` / `merge_redundant=` (merge_redundant only matters with merge)"""
+    return (POST_MERGE | (0 if merge_redundant else POST_MERGE_KEEP_SINGLE)) if merge else 0
 
 
 class PostDesc(C.Structure):

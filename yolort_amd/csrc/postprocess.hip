@@ -1406,6 +1406,255 @@ __global__ __launch_bounds__(256) void gather_topk_kernel(const GatherArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// 4a. the pieces of the gather as __device__ functions of the block size, for merge_gather_kernel (4b): its images outside the merge bound run gather_image /
+//     gather_finish -- gather_topk_kernel's statements, word for word -- and its merged images end with the same write_detection / gather_finish.  gather_topk_kernel
+//     itself keeps its own text above: restated through these functions it compiled to the same registers but not to the same instructions, and the default path is
+//     to stay byte for byte what it was.
+// ------------------------------------------------------------------------------------------
+// One detection into slot `rank` of image `img`: the box (already rescaled), the score bit-inverted back out of the record, the label; the same in the packed wire slab
+__device__ __forceinline__ void write_detection(const GatherArgs& a, unsigned img, int rank, const f32x4 o, uint64_t hi, uint32_t lo) {
+    const int64_t slot = (int64_t)img * a.K + rank;
+    *reinterpret_cast<f32x4*>(a.out_boxes + slot * 4) = o;
+    a.out_scores[slot] = __uint_as_float(~(uint32_t)hi);
+    a.out_labels[slot] = (int64_t)(lo & ((1u << a.label_bits) - 1u));
+    if (a.out_slab != nullptr) {   // the same detection in the packed wire slab (rows of 6K + 1 floats: only 4-byte aligned)
+        float* row = a.out_slab + (int64_t)img * (6 * a.K + 1);
+        row[4 * rank] = o[0]; row[4 * rank + 1] = o[1]; row[4 * rank + 2] = o[2]; row[4 * rank + 3] = o[3];
+        row[4 * a.K + rank] = __uint_as_float(~(uint32_t)hi);
+        row[5 * a.K + rank] = (float)(lo & ((1u << a.label_bits) - 1u));
+    }
+}
+
+__device__ __forceinline__ f32x4 rescale_box(const f32x4 b, float gain, float padx, float pady) {
+    f32x4 o = b;
+    if (gain > 0.f) {  // transform.py:362-365
+        o[0] = __fdiv_rn(__fsub_rn(b[0], padx), gain);
+        o[2] = __fdiv_rn(__fsub_rn(b[2], padx), gain);
+        o[1] = __fdiv_rn(__fsub_rn(b[1], pady), gain);
+        o[3] = __fdiv_rn(__fsub_rn(b[3], pady), gain);
+    }
+    return o;
+}
+
+// gather_topk_kernel's loop for ONE image and a block of NT threads: an ordered compaction of the keep flags of G's range [begin, end), the first K kept written out.
+// Leaves the number of kept records it counted (it stops counting once K are taken) in *s_taken.  The path of merge_gather_kernel's images outside the merge bound.
+template <int NT>
+__device__ __forceinline__ void gather_image(const GatherArgs& a, unsigned img, int begin, int end, float gain, float padx, float pady, int* wave_cnt, int* s_taken) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    for (int c = begin; c < end; c += NT) {
+        const int taken = *s_taken;
+        if (taken >= a.K) break;
+        const int r = c + threadIdx.x;
+        const bool k = r < end && a.keep[r] != 0;
+        const uint64_t m = __ballot(k);
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = taken;
+        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+        const int rank = off + __popcll(m & lt);
+        if (k && rank < a.K) {
+            const uint64_t hi = a.ghi[r];
+            const uint32_t lo = a.glo[r];
+            const unsigned anchor = lo >> a.label_bits;
+            const f32x4 b = *reinterpret_cast<const f32x4*>(a.boxes_all + ((int64_t)img * a.total_anchors + anchor) * 4);
+            write_detection(a, img, rank, rescale_box(b, gain, padx, pady), hi, lo);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int sum = taken;
+#pragma unroll
+            for (int w = 0; w < NT / 64; ++w) sum += wave_cnt[w];
+            *s_taken = sum;
+        }
+        __syncthreads();
+    }
+}
+
+// gather_topk_kernel's epilogue, whatever filled the image's slots: `cnt` detections were written, `taken` kept records were counted.  Zeroes the slab past the count, writes the
+// count, raises YMI_STATUS_PREFIX_SHORT for a truncated image that fell short, adds the raw count, and runs the last-block protocol (ST_DONE, YMI_SLAB_STALE).
+template <int NT>
+__device__ __forceinline__ void gather_finish(const GatherArgs& a, unsigned img, int n, int cnt, const int* s_taken, int* s_last) {
+    if (a.out_slab != nullptr) {   // slots past the count are zero: the slab is a function of the detections alone
+        float* row = a.out_slab + (int64_t)img * (6 * a.K + 1);
+        for (int t = cnt + (int)threadIdx.x; t < a.K; t += NT) {
+            row[4 * t] = 0.f; row[4 * t + 1] = 0.f; row[4 * t + 2] = 0.f; row[4 * t + 3] = 0.f;
+            row[4 * a.K + t] = 0.f;
+            row[5 * a.K + t] = 0.f;
+        }
+        if (threadIdx.x == 0) row[6 * a.K] = (float)cnt;
+    }
+    if (threadIdx.x == 0) {
+        a.out_count[img] = cnt;
+        // a truncated image must reach K survivors on its prefix alone, else the cut may have mattered
+        if (a.truncated != nullptr && a.truncated[img] != 0 && *s_taken < a.K) atomicOr(&a.status_rw[ST_OVERFLOW], YMI_STATUS_PREFIX_SHORT);
+        if (a.img_count != nullptr) atomicAdd(&a.status_rw[ST_RAW], a.img_count[img]);
+        else if (img == 0) atomicAdd(&a.status_rw[ST_RAW], n);
+        // last-block fix-up: the status word is final only when every image's block has finished (ST_DONE is zeroed by post_begin)
+        __threadfence();
+        *s_last = atomicAdd(&a.status_rw[ST_DONE], 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (*s_last && a.out_slab != nullptr) {
+        __threadfence();
+        if (atomicOr(&a.status_rw[ST_OVERFLOW], 0) != 0)   // the caller will re-run this batch: mark every row stale (yolort_amd/dist.py SLAB_STALE)
+            for (int i = threadIdx.x; i < (int)gridDim.x; i += NT) a.out_slab[(int64_t)i * (6 * a.K + 1) + 6 * a.K] = YMI_SLAB_STALE;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// 4b. merge-NMS (YMI_POST_MERGE; Python: merge=True; ultralytics' non_max_suppression with its local `merge = True`, yolort/v5/utils/general.py:604-613).  Launched
+//     INSTEAD of gather_topk_kernel, one workgroup of MRG_WAVES waves per image.  An image of n candidates is merged iff 1 < n < YMI_MERGE_MAX_N; every other image
+//     runs gather_image / gather_finish above and comes out as without the flag.  A merged image:
+//       1. its records (< YMI_MERGE_MAX_N of them: box, score, label) are staged in LDS in rank order;
+//       2. the first K kept ranks are compacted, in order, into an LDS list (the kept list is taken BEFORE the merge, general.py:604-605);
+//       3. wave w takes the kept records q = w, w + MRG_WAVES, ...: lane l walks the candidates j = l, l + 64, ... and, for those of the same label (any label under
+//          YMI_POST_AGNOSTIC) whose IoU with the kept box is > nms_thresh (iou_gt: the suppression's own test, so the box itself counts unless its area is 0), adds
+//          score_j and score_j * box_j to five partial sums with explicitly rounded fp32 multiplies and adds, and counts them; a fixed xor butterfly (32, 16, .., 1)
+//          sums the lanes -- fp32 addition commutes, so every lane ends with the same bits, and the order is a function of the candidate's rank alone;
+//       4. merged box = sums / weight (fp32 division) if the weight is > 0, else the NMS box; without YMI_POST_MERGE_KEEP_SINGLE a kept record with <= 1 contributors
+//          is dropped (general.py:612-613);
+//       5. the survivors are compacted in rank order, rescaled and written like any detection (write_detection); slots are not refilled.
+//     Dynamic LDS: merge_lds_bytes(K), 75000 + 16 * min(K, YMI_MERGE_MAX_N - 1) bytes (78 KiB at K = 300).
+// ------------------------------------------------------------------------------------------
+constexpr int MRG_WAVES = 16;
+constexpr int MRG_THREADS = MRG_WAVES * 64;
+constexpr int MRG_N = YMI_MERGE_MAX_N;
+
+inline int merge_kept_cap(int K) { return K < MRG_N - 1 ? K : MRG_N - 1; }   // a merged image has fewer than MRG_N records, hence fewer kept ones
+inline size_t merge_lds_bytes(int K) { return (size_t)MRG_N * (16 + 4 + 2 + 2 + 1) + (size_t)merge_kept_cap(K) * 16; }
+
+__global__ __launch_bounds__(MRG_THREADS) void merge_gather_kernel(const GatherArgs a, float thr, int agnostic, int keep_single, int kept_cap) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_key[];
+    __shared__ int wave_cnt[MRG_WAVES];
+    __shared__ int s_taken, s_kept;
+    __shared__ int s_last;
+    const int n = ncand(a.status, a.cap);
+    const unsigned img = blockIdx.x;
+    const int begin = lower_bound_img(a.ghi, n, img), end = lower_bound_img(a.ghi, n, img + 1);
+    const int ns = end - begin;                                              // records staged: the image's range in G
+    const int n_i = a.img_count != nullptr ? a.img_count[img] : ns;          // the image's candidate count
+    if (threadIdx.x == 0) s_taken = 0;
+    __syncthreads();
+    float gain = 0.f, padx = 0.f, pady = 0.f;
+    if (a.rescale) { gain = a.rescale[img * 3]; padx = a.rescale[img * 3 + 1]; pady = a.rescale[img * 3 + 2]; }
+    if (!(n_i > 1 && n_i < MRG_N) || ns >= MRG_N) {   // block-uniform: not a merged image (general.py:606).  A truncated image has > 6144 records: never merged
+        gather_image<MRG_THREADS>(a, img, begin, end, gain, padx, pady, wave_cnt, &s_taken);
+        gather_finish<MRG_THREADS>(a, img, n, s_taken < a.K ? s_taken : a.K, &s_taken, &s_last);
+        return;
+    }
+    f32x4* box = reinterpret_cast<f32x4*>(lds_key);                          // [MRG_N]
+    f32x4* merged = box + MRG_N;                                             // [kept_cap]
+    float* score = reinterpret_cast<float*>(merged + kept_cap);              // [MRG_N]
+    uint16_t* label = reinterpret_cast<uint16_t*>(score + MRG_N);            // [MRG_N]  (num_classes <= 4096)
+    uint16_t* kept = label + MRG_N;                                          // [MRG_N]  local rank of the q-th kept record
+    uint8_t* drop = reinterpret_cast<uint8_t*>(kept + MRG_N);                // [MRG_N]  1 = redundant
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const uint32_t lmask = (1u << a.label_bits) - 1u;
+    // 1. stage
+    for (int j = threadIdx.x; j < ns; j += MRG_THREADS) {
+        const uint64_t hi = a.ghi[begin + j];
+        const uint32_t lo = a.glo[begin + j];
+        box[j] = *reinterpret_cast<const f32x4*>(a.boxes_all + ((int64_t)img * a.total_anchors + (lo >> a.label_bits)) * 4);
+        score[j] = __uint_as_float(~(uint32_t)hi);
+        label[j] = (uint16_t)(lo & lmask);
+    }
+    // 2. the first K kept ranks, in order (gather_image's compaction, into the list)
+    for (int c = 0; c < ns; c += MRG_THREADS) {
+        const int taken = s_taken;
+        if (taken >= a.K) break;
+        const int j = c + threadIdx.x;
+        const bool k = j < ns && a.keep[begin + j] != 0;
+        const uint64_t m = __ballot(k);
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = taken;
+        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+        const int rank = off + __popcll(m & lt);
+        if (k && rank < a.K) kept[rank] = (uint16_t)j;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int sum = taken;
+#pragma unroll
+            for (int w = 0; w < MRG_WAVES; ++w) sum += wave_cnt[w];
+            s_taken = sum;
+        }
+        __syncthreads();
+    }
+    __syncthreads();   // the staged records and the list are complete (ns == 0 runs neither loop)
+    const int taken_all = s_taken;
+    const int nk = taken_all < a.K ? taken_all : a.K;   // <= kept_cap: nk <= ns < MRG_N
+    // 3. + 4. one wave per kept record
+    for (int q = wave; q < nk; q += MRG_WAVES) {   // wave-uniform
+        const int i = kept[q];
+        const f32x4 bi = box[i];
+        const float ai = __fmul_rn(__fsub_rn(bi[2], bi[0]), __fsub_rn(bi[3], bi[1]));
+        const unsigned li = label[i];
+        float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int m = 0;
+        for (int j = lane; j < ns; j += 64) {
+            if (!agnostic && label[j] != li) continue;
+            const f32x4 bj = box[j];
+            const float aj = __fmul_rn(__fsub_rn(bj[2], bj[0]), __fsub_rn(bj[3], bj[1]));
+            if (iou_gt(bi, ai, bj, aj, thr)) {
+                const float s = score[j];
+                sw = __fadd_rn(sw, s);
+                s0 = __fadd_rn(s0, __fmul_rn(s, bj[0]));
+                s1 = __fadd_rn(s1, __fmul_rn(s, bj[1]));
+                s2 = __fadd_rn(s2, __fmul_rn(s, bj[2]));
+                s3 = __fadd_rn(s3, __fmul_rn(s, bj[3]));
+                ++m;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            sw = __fadd_rn(sw, __shfl_xor(sw, d, 64));
+            s0 = __fadd_rn(s0, __shfl_xor(s0, d, 64));
+            s1 = __fadd_rn(s1, __shfl_xor(s1, d, 64));
+            s2 = __fadd_rn(s2, __shfl_xor(s2, d, 64));
+            s3 = __fadd_rn(s3, __shfl_xor(s3, d, 64));
+            m += __shfl_xor(m, d, 64);
+        }
+        if (lane == 0) {
+            f32x4 o = bi;
+            if (sw > 0.f) {   // all-zero scores (a non-positive score_thresh): the box keeps its NMS coordinates (the reference would divide by 0)
+                o[0] = __fdiv_rn(s0, sw); o[1] = __fdiv_rn(s1, sw); o[2] = __fdiv_rn(s2, sw); o[3] = __fdiv_rn(s3, sw);
+            }
+            merged[q] = o;
+            drop[q] = (!keep_single && m <= 1) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { s_kept = taken_all; s_taken = 0; }   // s_kept: what gather_finish compares with K for a truncated image (a merged image never is one)
+    __syncthreads();
+    // 5. the survivors, compacted in rank order
+    for (int c = 0; c < nk; c += MRG_THREADS) {
+        const int base = s_taken;
+        const int q = c + threadIdx.x;
+        const bool k = q < nk && drop[q] == 0;
+        const uint64_t m = __ballot(k);
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+        if (k) {
+            const int r = begin + kept[q];
+            write_detection(a, img, off + __popcll(m & lt), rescale_box(merged[q], gain, padx, pady), a.ghi[r], a.glo[r]);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int sum = base;
+#pragma unroll
+            for (int w = 0; w < MRG_WAVES; ++w) sum += wave_cnt[w];
+            s_taken = sum;
+        }
+        __syncthreads();
+    }
+    gather_finish<MRG_THREADS>(a, img, n, s_taken, &s_kept, &s_last);
+}
+
+// ------------------------------------------------------------------------------------------
 // host-side orchestration
 // ------------------------------------------------------------------------------------------
 
@@ -1435,7 +1684,7 @@ static bool nms_block_enabled() {
 // with label 0) under YMI_POST_AGNOSTIC, where a segment gets a workgroup (nms_block_kernel) instead of a wave
 static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint32_t* plo, int* status, int cap, int n_img, int label_bits, int total_anchors,
                       float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count, hipStream_t s,
-                      const int* truncated = nullptr, float* out_slab = nullptr, const int* img_count = nullptr, bool agnostic = false) {
+                      const int* truncated = nullptr, float* out_slab = nullptr, const int* img_count = nullptr, bool agnostic = false, int merge_flags = 0) {
     const int nthr_blocks = cdiv(cap, 256);
     uint32_t* seg_start = w.seg_start;
     float* kept_box = w.kept_box;
@@ -1451,6 +1700,13 @@ static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint
     ga.truncated = truncated; ga.status_rw = status; ga.out_slab = out_slab; ga.img_count = img_count;
     ga.cap = cap; ga.total_anchors = total_anchors; ga.label_bits = label_bits; ga.K = K;
     ga.out_boxes = out_boxes; ga.out_scores = out_scores; ga.out_labels = out_labels; ga.out_count = out_count;
+    if (merge_flags & YMI_POST_MERGE) {   // merge-NMS: the reduction and the gather in one kernel, launched instead of the plain gather
+        const size_t lds = merge_lds_bytes(K);
+        if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)merge_gather_kernel, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
+        hipLaunchKernelGGL(merge_gather_kernel, dim3(n_img), dim3(MRG_THREADS), lds, s, ga, nms_thresh, agnostic ? 1 : 0, (merge_flags & YMI_POST_MERGE_KEEP_SINGLE) ? 1 : 0,
+                           merge_kept_cap(K));
+        return check_launch("nms/merge_gather");
+    }
     hipLaunchKernelGGL(gather_topk_kernel, dim3(n_img), dim3(256), 0, s, ga);
     return check_launch("nms/gather");
 }
@@ -1458,7 +1714,7 @@ static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint
 // sorts records in w.hi/lo[st.cur] by (img, score desc, cand asc), then runs NMS + gather.
 static int sort_nms_gather(const Workspace& w, SortState st, int* status, int cap, int n_img, int lo_bits, int label_bits, int total_anchors,
                            float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count,
-                           hipStream_t s, float* out_slab = nullptr, bool agnostic = false) {
+                           hipStream_t s, float* out_slab = nullptr, bool agnostic = false, int merge_flags = 0) {
     int rc;
     for (int sh = 0; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
     for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
@@ -1493,7 +1749,7 @@ static int sort_nms_gather(const Workspace& w, SortState st, int* status, int ca
     }
     (void)label_passes;
     return nms_gather(w, g, phi, plo, status, cap, n_img, label_bits, total_anchors, nms_thresh, K, rescale, out_boxes, out_scores, out_labels, out_count, s, nullptr, out_slab,
-                      nullptr, agnostic);
+                      nullptr, agnostic, merge_flags);
 }
 
 // The batch size a descriptor may carry: the per-image path ranks the whole batch through one LDS table (rank_image_kernel), and include/yolort_amd.h gives that limit
@@ -1511,6 +1767,7 @@ static int post_validate(const ymi_post_desc* d, bool need_logits, PostLayout& L
     YMI_REQUIRE(d->num_classes >= 1 && d->num_classes <= 4096, "ymi_postprocess: num_classes %d out of range", d->num_classes);
     YMI_REQUIRE(d->out_boxes && d->out_scores && d->out_labels && d->out_count && d->status && d->ws, "ymi_postprocess: null buffer");
     YMI_REQUIRE(d->detections_per_img >= 1 && d->cand_cap >= 1, "ymi_postprocess: detections_per_img and cand_cap must be positive");
+    YMI_REQUIRE((d->flags & YMI_POST_MERGE) != 0 || (d->flags & YMI_POST_MERGE_KEEP_SINGLE) == 0, "ymi_postprocess: YMI_POST_MERGE_KEEP_SINGLE without YMI_POST_MERGE");
     for (int l = 0; l < d->num_levels; ++l) {
         YMI_REQUIRE(d->lh[l] >= 1 && d->lw[l] >= 1, "ymi_postprocess: level %d has an empty grid", l);
         if (need_logits) {
@@ -1603,6 +1860,7 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
     if (rc != YMI_OK) return rc;
     const bool agnostic = (d->flags & YMI_POST_AGNOSTIC) != 0;
     const int p_bits = agnostic ? 0 : L.label_bits;   // label bits of the P keys: none under YMI_POST_AGNOSTIC (P is G's order, one segment per image)
+    const int merge_flags = d->flags & (YMI_POST_MERGE | YMI_POST_MERGE_KEEP_SINGLE);   // merge-NMS: merge_gather_kernel instead of gather_topk_kernel
     if (L.per_image) {
         const int cap_img = L.cap_img;
         const bool exact_full = (d->flags & YMI_POST_EXACT_FULL) != 0;
@@ -1652,13 +1910,13 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
                                RANK_MAX, w.hi[1], w.lo[1], w.p_hi, w.p_lo, w.keep, d->status);
         if ((rc = check_launch("select_prefix/sort_image")) != YMI_OK) return rc;
         return nms_gather(w, 1, w.p_hi, w.p_lo, d->status, d->cand_cap, d->n, L.label_bits, L.total_anchors, d->nms_thresh, d->detections_per_img, d->rescale,
-                          d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, w.sel_count + d->n, d->out_slab, w.img_count, agnostic);
+                          d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, w.sel_count + d->n, d->out_slab, w.img_count, agnostic, merge_flags);
     }
     hipLaunchKernelGGL(finalize_count_kernel, dim3(1), dim3(64), 0, s, d->status, d->cand_cap);
     rc = check_launch("finalize_count");
     if (rc != YMI_OK) return rc;
     return sort_nms_gather(w, SortState{0}, d->status, d->cand_cap, d->n, L.label_bits + L.anchor_bits, L.label_bits, L.total_anchors, d->nms_thresh,
-                           d->detections_per_img, d->rescale, d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, d->out_slab, agnostic);
+                           d->detections_per_img, d->rescale, d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, d->out_slab, agnostic, merge_flags);
 }
 
 int postprocess_launch(const ymi_post_desc* d, hipStream_t s) {

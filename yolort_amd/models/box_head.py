@@ -114,12 +114,18 @@ class PostProcess(nn.Module):
     born -- before NMS and top-k, so no slot of `detections_per_img` goes to an unwanted class and, with `agnostic`, no unwanted box suppresses a wanted one.  With
     multi_label=False the best class is still taken over all classes, and an anchor whose best class is not allowed yields nothing.  `[]` gives no detections.  A live
     attribute too: a new SET takes effect on the next batch without a new plan (the set is data in the plan's workspace); only None <-> a set selects another plan.
-    ValueError for a non-integer or negative index here, for an index >= num_classes at the next batch (or at the model's construction)."""
+    ValueError for a non-integer or negative index here, for an index >= num_classes at the next batch (or at the model's construction).
+    `merge` (an attribute, default False; ultralytics' local `merge = True`, general.py:604-613): merge-NMS -- in an image of 1 < n < 3000 candidates every kept box becomes
+    the score-weighted mean of the candidates of its class (any class with `agnostic`) whose IoU with it is above nms_thresh; scores and labels stay.  `merge_redundant`
+    (an attribute, default True; ultralytics' `redundant`): a kept box with no contributor but itself is dropped, so fewer than `detections_per_img` detections can come
+    out although more boxes were kept; False keeps them.  Both are live attributes: a change takes effect on the next batch (through a plan of its own)."""
 
     def __init__(self, strides: List[int], score_thresh: float, nms_thresh: float, detections_per_img: int, multi_label: bool = True, agnostic: bool = False) -> None:
         super().__init__()
         self.multi_label = multi_label
         self.agnostic = agnostic
+        self.merge = False          # (attributes, like `classes`: the parameter list stays)
+        self.merge_redundant = True
         self.classes = None   # (the constructor's parameter list is the one it was: YOLO(...), the factories and YOLOv5(...) take `classes=` and set it here)
         self.strides = strides
         self.score_thresh = score_thresh
@@ -146,4 +152,4 @@ class PostProcess(nn.Module):
             anchors.append(a)
         k = head_outputs[0].shape[-1]
         return postprocess_logits(head_outputs, [float(s) for s in self.strides], anchors, k - 5, self.score_thresh, self.nms_thresh, self.detections_per_img,
-                                  multi_label=self.multi_label, agnostic=self.agnostic, classes=self.classes)
+                                  multi_label=self.multi_label, agnostic=self.agnostic, classes=self.classes, merge=self.merge, merge_redundant=self.merge_redundant)

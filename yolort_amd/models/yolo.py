@@ -14,7 +14,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor, nn
 
-from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_CLASS_FILTER, POST_EXACT_FULL, YmiError, check, normalize_classes
+from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_CLASS_FILTER, POST_EXACT_FULL, YmiError, check, merge_flags, normalize_classes
 from ..engine import Plan, View
 from ..hipmodule import compute_dtype_of, nchw_to_view, view_to_nchw, weights_signature
 from ..ops import slab_to_list
@@ -179,6 +179,8 @@ class YOLO(nn.Module):
         multi_label: bool = True,
         agnostic: bool = False,
         classes: Optional[Sequence[int]] = None,
+        merge: bool = False,
+        merge_redundant: bool = True,
     ):
         super().__init__()
         if not hasattr(backbone, "out_channels"):
@@ -196,6 +198,9 @@ class YOLO(nn.Module):
         self.post_process = post_process if post_process is not None else PostProcess(self.anchor_generator.strides, score_thresh, nms_thresh, detections_per_img, multi_label=multi_label, agnostic=agnostic)
         if post_process is None:
             self.post_process.classes = normalize_classes(classes, num_classes)
+            self.post_process.merge, self.post_process.merge_redundant = bool(merge), bool(merge_redundant)
+        elif merge or not merge_redundant:   # as for classes= below
+            raise ValueError("merge= / merge_redundant= configure the package's own PostProcess: with an injected post_process, set the attributes on that module")
         elif classes is not None:   # an injected module is taken as it is: a set given next to it would be dropped without a word
             raise ValueError("classes= configures the package's own PostProcess: with an injected post_process, set the filter on that module")
         self.compute_dtype = torch.float16  # used when parameters are fp32 (see hipmodule.compute_dtype_of)
@@ -298,7 +303,9 @@ class YOLO(nn.Module):
         if classes and classes[-1] >= self.num_classes:   # (sorted: the largest index last)
             raise ValueError(f"post_process.classes: index {classes[-1]} outside [0, {self.num_classes})")
         key = (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True)), bool(getattr(pp, "agnostic", False)))
-        return key if classes is None else key + (True,)   # (the key of a model without a filter is the one it always was)
+        key = key if classes is None else key + (True,)   # (the key of a model without a filter is the one it always was)
+        mf = merge_flags(bool(getattr(pp, "merge", False)), bool(getattr(pp, "merge_redundant", True)))
+        return key + (("merge", mf),) if mf else key   # (... and so is the key of a model without merge-NMS; the element is a pair: never the filter's True)
 
     def _entry(self, n: int, h: int, w: int, device: torch.device, classes=_LIVE) -> _PlanEntry:
         """a plan instance of this shape whose previous batch has been collected by the host.  Instances are built lazily
@@ -379,7 +386,7 @@ class YOLO(nn.Module):
             ag = self.anchor_generator
             strides = [float(s) for s in ag.strides]
             args = (self.num_classes, float(pp.score_thresh), float(pp.nms_thresh), int(pp.detections_per_img), self.cand_cap_per_image * n)
-            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0) | (POST_CLASS_FILTER if self._classes(classes) is not None else 0)   # rebuilt plans (capacity growth, exact full pass) come through here too
+            flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0) | (POST_CLASS_FILTER if self._classes(classes) is not None else 0) | merge_flags(bool(getattr(pp, "merge", False)), bool(getattr(pp, "merge_redundant", True)))   # rebuilt plans (capacity growth, exact full pass) come through here too
             if self.fuse_head_decode and self.head.can_fuse_decode(plan, feats):
                 post, pd = plan.post_desc([(f.h, f.w) for f in feats], n, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
                 plan.post_begin(pd)
@@ -557,7 +564,8 @@ class YOLO(nn.Module):
 
     @classmethod
     def load_from_yolov5(cls, checkpoint_path: str, score_thresh: float = 0.25, nms_thresh: float = 0.45, version: str = "r6.0",
-                         post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False, classes: Optional[Sequence[int]] = None):
+                         post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False, classes: Optional[Sequence[int]] = None,
+                         merge: bool = False, merge_redundant: bool = True):
         """Load model state from a checkpoint trained by ultralytics/yolov5 (reference yolo.py:185-223)."""
         from ._checkpoint import load_from_ultralytics
 
@@ -565,7 +573,7 @@ class YOLO(nn.Module):
         backbone_name = f"darknet_{info['size']}_{version.replace('.', '_')}"
         backbone = darknet_pan_backbone(backbone_name, info["depth_multiple"], info["width_multiple"], version=version, use_p6=info["use_p6"])
         model = cls(backbone, info["num_classes"], strides=info["strides"], anchor_grids=info["anchor_grids"], score_thresh=score_thresh,
-                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic, classes=classes)
+                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic, classes=classes, merge=merge, merge_redundant=merge_redundant)
         model.load_state_dict(info["state_dict"])
         return model
 

@@ -72,10 +72,12 @@ def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence
 
 def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float], anchors: Sequence[Sequence[float]], num_classes: int,
                        score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: Optional[int] = None, multi_label: bool = True, agnostic: bool = False,
-                       classes: Optional[Sequence[int]] = None) -> List[Dict[str, Tensor]]:
+                       classes: Optional[Sequence[int]] = None, merge: bool = False, merge_redundant: bool = True) -> List[Dict[str, Tensor]]:
     """Runs the fused post-process on reference-layout head outputs [(N,A,H,W,K)] (A == 3).  multi_label=False: one label per anchor, its best class
     (include/yolort_amd.h YMI_POST_BEST_CLASS).  agnostic=True: one NMS over all boxes of an image, whatever their label (YMI_POST_AGNOSTIC).  classes=[...]: only candidates of these classes, filtered
-    before NMS and top-k (YMI_POST_CLASS_FILTER; multi_label=False: an anchor whose best class is not in the set yields nothing); None = no filter."""
+    before NMS and top-k (YMI_POST_CLASS_FILTER; multi_label=False: an anchor whose best class is not in the set yields nothing); None = no filter.  merge=True: merge-NMS (YMI_POST_MERGE) -- in an image of
+    1 < n < 3000 candidates every kept box becomes the score-weighted mean of the candidates of its class (any class with agnostic) whose IoU with it is above nms_thresh, and
+    a box with no contributor but itself is dropped unless merge_redundant=False (YMI_POST_MERGE_KEEP_SINGLE)."""
     classes = _lib.normalize_classes(classes, num_classes)
     _lib.load(require_gpu=True)
     h0 = head_outputs[0]
@@ -92,7 +94,7 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
         nhwc[..., : 3 * k] = ho.to(torch.float32).permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * k)
         plan_inputs.append(nhwc)
     cap = cand_cap or max(4096, 2048 * n)
-    flags = (0 if multi_label else _lib.POST_BEST_CLASS) | (_lib.POST_AGNOSTIC if agnostic else 0)
+    flags = (0 if multi_label else _lib.POST_BEST_CLASS) | (_lib.POST_AGNOSTIC if agnostic else 0) | _lib.merge_flags(merge, merge_redundant)
     while True:
         plan = Plan(h0.device, torch.float16)
         views = [View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * k, t.shape[3]) for t in plan_inputs]
