@@ -71,6 +71,26 @@ int ymi_device_count(void);
 int ymi_letterbox(const void* const* imgs, const int32_t* geom, int n, int in_dtype, void* out, int hb,
                   int wb, int c_out, int out_dtype, float fill, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View canvas of augmented inference (test-time augmentation): a scaled, optionally left-right mirrored copy of the
+ * letterboxed NHWC4 canvas.  Replaces yolort/v5/utils/torch_utils.py:288-300 (scale_img: F.interpolate bilinear,
+ * align_corners=False, then F.pad with 0.447) and the x.flip(3) of yolort/v5/models/yolo.py:158, in one launch.
+ *   src   (n, h, w, 4) NHWC4 of `dtype` (YMI_F16 / YMI_BF16 / YMI_F32); channel 3 is not read
+ *   dst   (n, dh, dw, 4) NHWC4 of the same dtype; channel 3 is written as zero (the layout the stem reads)
+ *   sh,sw the resized size, 1 <= sh <= dh, 1 <= sw <= dw.  The host computes the sizes as the reference does, in Python
+ *         floats: sh, sw = int(h * r), int(w * r); dh, dw = ceil(h * r / gs) * gs, ceil(w * r / gs) * gs (gs = largest stride)
+ *   flip  != 0: column x of the source is column w - 1 - x of `src` (mirror first, then scale, as the reference does)
+ * Pixels inside (sh, sw): ATen's upsample_bilinear2d -- source index (dst + 0.5) * (in / out) - 0.5 (in / out rounded to fp32, then ONE
+ * fused multiply-add: the exact expression rounded once, as ATen's CPU kernel computes it) clamped at 0, second tap clamped at in - 1,
+ * weights l1 = index - floor, l0 = 1 - l1, in fp32.  The value is mathematically h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11); it is
+ * evaluated over the four tap weights w_ij = fl(h_i * w_j) as fma(w11, v11, fma(w10, v10, fma(w00, v00, fl(w01 * v01)))) -- the order in which
+ * the result equals F.interpolate bit for bit when the weights are powers of two (ratio 0.5); the nested form is an ulp away from it there --
+ * then ONE rounding to `dtype`.  Pixels outside: 0.447 rounded to `dtype`.
+ * Nothing outside dst's n * dh * dw pixels is written.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_VIEW_PAD 0.447f
+int ymi_scale_view(const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype, void* stream);
+
 /* NCHW (n,c,h,w) -> NHWC view and back (module-level API edges; not on the fused path). */
 int ymi_nchw_to_nhwc(const void* x, int n, int c, int h, int w, int in_dtype, void* y, int y_cstride,
                      int c_pad, int out_dtype, void* stream);
@@ -378,6 +398,50 @@ int ymi_postprocess(const ymi_post_desc* d, void* stream);
 int ymi_post_begin(const ymi_post_desc* d, void* stream);
 int ymi_post_finish(const ymi_post_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Augmented inference (test-time augmentation): ultralytics' DetectionModel.forward(x, augment=True) -> _forward_augment
+ * (yolort/v5/models/yolo.py:147-163), what AutoShape.forward(imgs, size, augment) exposes.  The letterboxed batch runs three
+ * times -- scale 1, scale 0.83 mirrored left-right, scale 0.67 (ymi_scale_view makes the two smaller canvases) --, the
+ * predictions of each view are brought back to the full canvas (_descale_pred, yolo.py:181-197), the views are concatenated
+ * along the anchor axis without the "tails" (_clip_augmented, yolo.py:199-208) and ONE NMS runs over the union.
+ *
+ * ymi_post_decode_view is a candidate producer between ymi_post_begin and ymi_post_finish: decode_kernel's twin for ONE view.
+ *   sink  an ordinary ymi_post_desc whose levels describe the CONCATENATED anchor axis of all views; begin / finish / this call
+ *         use its geometry only for the anchor count A = sum 3 * lh * lw, so one pseudo-level of 1 x (A / 3) does (logits[],
+ *         lcstride[], stride[] and anchors[] of the sink are ignored here).  Thresholds, num_classes, flags (best-class mode,
+ *         class filter), capacity and workspace are the sink's: scores, the strict threshold, YMI_POST_BEST_CLASS and
+ *         YMI_POST_CLASS_FILTER behave exactly as in ymi_postprocess.
+ *   view  geometry, fp32 NHWC logits (n of the sink, channel a * K + k), strides and anchors of this view's pyramid, and
+ *         skip_mask    bit l set: level l contributes nothing and occupies NO anchor indices (the clipped tail)
+ *         anchor_base  index of the view's first kept anchor within an image of the sink; the kept levels follow each other from
+ *                      there in level order, anchor index within a level = (a * lh + y) * lw + x as ever.  Records carry
+ *                      anchor_base + index, so the sort's tie order is view-major, then anchor, then class -- torch.cat(y, 1)'s --
+ *                      and the decoded box of every kept anchor is stored at that index.
+ *         scale, flip_w  the decoded box (x1, y1, x2, y2) of ymi_postprocess's decode is mapped to the full canvas in explicitly
+ *                      rounded fp32: y1' = y1 / scale, y2' = y2 / scale; flip_w == 0: x1' = x1 / scale, x2' = x2 / scale;
+ *                      flip_w = W > 0 (the full canvas width, the view was mirrored): x1' = W - x2 / scale, x2' = W - x1 / scale.
+ * Which levels to skip: view 0 every level but the coarsest, the last view every level but the finest, the others none --
+ * since every view's sides are multiples of the largest stride this is exactly what _clip_augmented cuts, for 3 and 4 levels.
+ * Differences from the reference: it applies / scale and W - x to the centre and the size (xywh) and converts to corners
+ * afterwards; here the corners themselves are divided and mirrored -- the two differ in rounding only (a few fp32 ulps of the
+ * coordinate).  The NMS is this library's (true class-aware, no 4096-pixel class offset, no max_nms cut), as for every mode above.
+ * The view must cover the sink's range: anchor_base + kept anchors <= A, else YMI_EINVAL.  ABI stays 6: a new struct and new
+ * functions only, no existing struct changed -- a caller built against the previous header keeps working.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ymi_post_view {
+    const float* logits[YMI_MAX_LEVELS];
+    int32_t lh[YMI_MAX_LEVELS], lw[YMI_MAX_LEVELS], lcstride[YMI_MAX_LEVELS];
+    float stride[YMI_MAX_LEVELS];
+    float anchors[YMI_MAX_LEVELS][6];
+    int32_t num_levels;
+    int32_t skip_mask;
+    int32_t anchor_base;
+    float scale;
+    int32_t flip_w;
+    int32_t reserved;
+} ymi_post_view;
+int ymi_post_decode_view(const ymi_post_desc* sink, const ymi_post_view* view, void* stream);
+
 /* YMI_POST_CLASS_FILTER: byte offset of the class mask (uint32[128], 256-byte aligned) inside a workspace of ymi_postprocess_ws_bytes(n, total_anchors, cand_cap)
  * bytes, for consumers who write the mask themselves; negative for arguments that have no workspace. */
 int64_t ymi_post_class_mask_offset(int n, int total_anchors, int cand_cap);
@@ -433,6 +497,10 @@ int ymi_plan_add_post_begin(ymi_plan* p, const ymi_post_desc* d);
 int ymi_plan_add_head_decode(ymi_plan* p, const ymi_conv_desc* conv, const ymi_post_desc* d, int level);
 int ymi_plan_add_head_decode_group(ymi_plan* p, const ymi_conv_desc* convs, int n_levels, const ymi_post_desc* d);
 int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d);
+/* augmented inference: ymi_scale_view / ymi_post_decode_view as recorded ops (the view's candidates belong to the post-process of `sink`:
+ * ymi_plan_set_classes writes that workspace's mask once, and an exported plan carries both descriptors) */
+int ymi_plan_add_scale_view(ymi_plan* p, const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype);
+int ymi_plan_add_post_decode_view(ymi_plan* p, const ymi_post_desc* sink, const ymi_post_view* view);
 int ymi_plan_num_ops(const ymi_plan* p);
 /* ymi_post_set_classes for every post-process descriptor recorded in the plan that carries YMI_POST_CLASS_FILTER (YMI_EINVAL if none does).  The plan remembers the
  * list: ymi_plan_export stores it, and ymi_plan_import writes the masks again before it returns, so an imported plan filters as the exporting one did; the consumer

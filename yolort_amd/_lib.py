@@ -94,6 +94,48 @@ class PostDesc(C.Structure):
     ]
 
 
+class PostView(C.Structure):
+    """ymi_post_view: one view of augmented inference for ymi_post_decode_view (its levels, the levels to skip, its anchor base, scale and mirror width)"""
+    _fields_ = [
+        ("logits", C.c_void_p * MAX_LEVELS),
+        ("lh", C.c_int32 * MAX_LEVELS), ("lw", C.c_int32 * MAX_LEVELS), ("lcstride", C.c_int32 * MAX_LEVELS),
+        ("stride", C.c_float * MAX_LEVELS),
+        ("anchors", (C.c_float * 6) * MAX_LEVELS),
+        ("num_levels", C.c_int32), ("skip_mask", C.c_int32), ("anchor_base", C.c_int32),
+        ("scale", C.c_float), ("flip_w", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+VIEW_PAD = 0.447   # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
+TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
+
+
+def tta_view_size(h: int, w: int, ratio: float, gs: int = 32):
+    """scale_img's sizes (yolort/v5/utils/torch_utils.py:296-299) in Python floats, exactly as the reference computes them: the resized size (sh, sw) and the
+    gs-multiple canvas (H', W') it is padded into; ratio 1.0 is the canvas itself"""
+    import math
+    if ratio == 1.0:
+        return (h, w), (h, w)
+    return (int(h * ratio), int(w * ratio)), (math.ceil(h * ratio / gs) * gs, math.ceil(w * ratio / gs) * gs)
+
+
+def tta_layout(view_levels, num_views=None):
+    """The concatenated anchor axis of augmented inference (_clip_augmented, yolo.py:199-208): view_levels[v] = [(h, w)] per pyramid level of view v.  View 0 drops its
+    coarsest level, the last view its finest; skipped levels occupy no indices.  Returns ([(skip_mask, anchor_base)] per view, total anchors)."""
+    nv = len(view_levels)
+    out, base = [], 0
+    for v, levels in enumerate(view_levels):
+        nl = len(levels)
+        skip = 0
+        if nv > 1 and v == 0:
+            skip |= 1 << (nl - 1)
+        if nv > 1 and v == nv - 1:
+            skip |= 1
+        out.append((skip, base))
+        base += sum(3 * h * w for l, (h, w) in enumerate(levels) if not (skip >> l) & 1)
+    return out, base
+
+
 _SIGS = {
     "ymi_abi_version": (C.c_int, []),
     "ymi_last_error": (C.c_char_p, []),
@@ -123,6 +165,10 @@ _SIGS = {
     "ymi_postprocess": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
     "ymi_post_begin": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
     "ymi_post_finish": (C.c_int, [C.POINTER(PostDesc), C.c_void_p]),
+    "ymi_post_decode_view": (C.c_int, [C.POINTER(PostDesc), C.POINTER(PostView), C.c_void_p]),
+    "ymi_plan_add_post_decode_view": (C.c_int, [C.c_void_p, C.POINTER(PostDesc), C.POINTER(PostView)]),
+    "ymi_scale_view": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ymi_plan_add_scale_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ymi_post_class_mask_offset": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "ymi_post_set_classes": (C.c_int, [C.POINTER(PostDesc), C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
     "ymi_plan_set_classes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_void_p]),

@@ -61,8 +61,9 @@ int post_check_batch(const ymi_post_desc* d);
 int post_set_classes_launch(const ymi_post_desc* d, const int32_t* classes, int count, hipStream_t s);
 int conv_head_decode_launch(const ymi_conv_desc* d, const ymi_post_desc* post, int level, hipStream_t s);
 int conv_head_decode_group_launch(const ymi_conv_desc* descs, int n_levels, const ymi_post_desc* post, hipStream_t s);
+int post_decode_view_launch(const ymi_post_desc* d, const ymi_post_view* v, hipStream_t s);
 
-enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT };
+enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW };
 
 struct Op {
     OpKind kind;
@@ -74,6 +75,7 @@ struct Op {
     const void* x;
     void* y;
     int i[8];
+    ymi_post_view view;   // OP_POST_VIEW: one view of augmented inference (its sink is `post`)
 };
 
 static int run_op(const Op& op, hipStream_t s) {
@@ -89,6 +91,8 @@ static int run_op(const Op& op, hipStream_t s) {
         case OP_POST_FINISH: return post_finish_launch(&op.post, s);
         case OP_C3_FUSED: return c3_fused_launch(&op.c3, s);
         case OP_ACT: return ymi_act(op.y, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.x, op.i[5], s);
+        case OP_SCALE_VIEW: return ymi_scale_view(op.x, op.i[0], op.i[1], op.i[2], op.y, op.i[3], op.i[4], op.i[5], op.i[6], op.i[7] & 1, op.i[7] >> 1, s);
+        case OP_POST_VIEW: return post_decode_view_launch(&op.post, &op.view, s);
     }
     set_error("unknown op kind");
     return YMI_EINVAL;
@@ -298,12 +302,38 @@ extern "C" int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d) {
     return add_post_op(p, OP_POST_FINISH, d, nullptr, 0);
 }
 
+extern "C" int ymi_plan_add_scale_view(ymi_plan* p, const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype) {
+    YMI_REQUIRE(p && src && dst, "ymi_plan_add_scale_view: null argument");
+    YMI_REQUIRE(dtype >= 0 && dtype < 64, "ymi_plan_add_scale_view: bad dtype %d", dtype);
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_SCALE_VIEW;
+    op.x = src; op.y = dst;
+    op.i[0] = n; op.i[1] = h; op.i[2] = w; op.i[3] = dh; op.i[4] = dw; op.i[5] = sh; op.i[6] = sw; op.i[7] = (dtype << 1) | (flip ? 1 : 0);
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
+extern "C" int ymi_plan_add_post_decode_view(ymi_plan* p, const ymi_post_desc* sink, const ymi_post_view* view) {
+    YMI_REQUIRE(p && sink && view, "ymi_plan_add_post_decode_view: null argument");
+    if (const int rc = post_check_batch(sink)) return rc;
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_POST_VIEW;
+    op.post = *sink;
+    op.view = *view;
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
 extern "C" int ymi_plan_num_ops(const ymi_plan* p) { return p ? (int)p->ops.size() : 0; }
 
 // the class mask of every post-process descriptor of the plan that carries YMI_POST_CLASS_FILTER (begin / head / finish ops of one post-process share a workspace: written once)
 static int plan_write_classes(const ymi_plan* p, const int32_t* classes, int count, hipStream_t s) {
     auto filtered = [](const Op& op) {
-        const bool post = op.kind == OP_POST || op.kind == OP_POST_BEGIN || op.kind == OP_HEAD_DECODE || op.kind == OP_HEAD_GROUP || op.kind == OP_POST_FINISH;
+        const bool post = op.kind == OP_POST || op.kind == OP_POST_BEGIN || op.kind == OP_HEAD_DECODE || op.kind == OP_HEAD_GROUP || op.kind == OP_POST_FINISH || op.kind == OP_POST_VIEW;
         return post && (op.post.flags & YMI_POST_CLASS_FILTER) != 0;
     };
     // the list is checked against EVERY descriptor before the first mask is written: a refused call leaves every workspace as it was
@@ -517,6 +547,7 @@ static void for_each_pointer(Op& op, F&& f) {   // every device-pointer field of
     f((void**)&c3.x); f((void**)&c3.y); f((void**)&c3.w12); f((void**)&c3.b12); f((void**)&c3.wm1); f((void**)&c3.bm1); f((void**)&c3.wm2); f((void**)&c3.bm2);
     f((void**)&c3.w3); f((void**)&c3.b3); f((void**)&c3.wblob); f((void**)&c3.y1_in); f((void**)&c3.y1_out); f((void**)&c3.y2);
     f((void**)&op.x); f((void**)&op.y);
+    for (int l = 0; l < YMI_MAX_LEVELS; ++l) f((void**)&op.view.logits[l]);
 }
 struct PlanFileHeader {
     char magic[8];            // "YMIPLAN1"

@@ -213,6 +213,174 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
     flush();
 }
 
+// ------------------------------------------------------------------------------------------
+// 1b. decode + threshold of ONE VIEW of augmented inference (ymi_post_decode_view; ultralytics' _forward_augment, yolort/v5/models/yolo.py:152-163): decode_kernel's twin.
+//     decode_kernel keeps its own text (and with it its instructions: the default path must not move); this kernel restates it with two differences, both in the three
+//     box lanes: the decoded corners are brought back to the full canvas (_descale_pred, yolo.py:181-197 -- y' = y / scale, x' = x / scale, or mirrored
+//     x1' = W - x2 / scale, x2' = W - x1 / scale; every operation an explicitly rounded fp32 one), and `level_off` already holds the view's anchor base plus the kept levels
+//     in front of this one, so records and boxes land in the view's range of the concatenated anchor axis (torch.cat(y, 1) after _clip_augmented).  Scores, thresholds,
+//     best-class mode and the class filter are decode_kernel's statements.
+// ------------------------------------------------------------------------------------------
+struct DecodeViewArgs {
+    DecodeArgs d;
+    float scale;           // the view's scale (boxes are divided by it)
+    float flip_w;          // > 0: the view was mirrored left-right, the full canvas width W as a float; 0: not mirrored
+};
+
+__device__ __forceinline__ f32x4 descale_box(const f32x4 b, float scale, float flip_w) {
+    const float x1 = __fdiv_rn(b[0], scale), y1 = __fdiv_rn(b[1], scale), x2 = __fdiv_rn(b[2], scale), y2 = __fdiv_rn(b[3], scale);
+    f32x4 o = {x1, y1, x2, y2};
+    if (flip_w > 0.f) {
+        o[0] = __fsub_rn(flip_w, x2);
+        o[2] = __fsub_rn(flip_w, x1);
+    }
+    return o;
+}
+
+__global__ __launch_bounds__(256) void decode_view_kernel(const DecodeViewArgs va) {
+    __shared__ uint64_t buf_hi[4][DEC_BUF];
+    __shared__ uint32_t buf_lo[4][DEC_BUF];
+    const DecodeArgs& a = va.d;
+    const CandSink& k_ = a.sink;
+    const int lane = threadIdx.x & 63;
+    const int wl = threadIdx.x >> 6;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + wl;
+    const int64_t npix = (int64_t)a.n * a.h * a.w;
+    const int hw = a.h * a.w;
+    const int nch = 3 * a.K;
+    const int npass = cdiv(nch, 256);
+    uint64_t* bhi = buf_hi[wl];
+    uint32_t* blo = buf_lo[wl];
+    int fill = 0;      // records in the LDS buffer (wave-uniform)
+    int fill_img = 0;  // image the buffered records belong to (per-image path flushes on image change)
+
+    auto flush = [&]() {
+        flush_records(k_, bhi, blo, fill, fill_img, lane);
+        __builtin_amdgcn_wave_barrier();   // see decode_kernel
+        fill = 0;
+    };
+
+    for (int pp = 0; pp < DEC_PIX_PER_WAVE; ++pp) {
+        const int64_t pix = wave * DEC_PIX_PER_WAVE + pp;
+        if (pix >= npix) break;
+        const int img = (int)(pix / hw);
+        const int rem = (int)(pix - (int64_t)img * hw);
+        const int y = rem / a.w, x = rem - y * a.w;
+        const float* row = a.logits + pix * a.cs;
+        float obj[3];
+        bool any_obj = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            obj[k] = sigmoid_acc(row[k * a.K + 4]);
+            any_obj |= obj[k] > k_.thr;
+        }
+        if (lane < 3) {
+            const float* r = row + lane * a.K;
+            const f32x4 b = descale_box(decode_box(r[0], r[1], r[2], r[3], x, y, a.stride, a.anc[2 * lane], a.anc[2 * lane + 1]), va.scale, va.flip_w);
+            const int anchor = a.level_off + (lane * a.h + y) * a.w + x;
+            *reinterpret_cast<f32x4*>(k_.boxes_all + ((int64_t)img * k_.total_anchors + anchor) * 4) = b;
+        }
+        if (!any_obj) continue;
+        if (fill + (k_.best ? 3 : nch) > DEC_BUF || img != fill_img) flush();
+        fill_img = img;
+        if (k_.best) {
+            BestClass b0 = best_none(), b1 = best_none(), b2 = best_none();
+            for (int p = 0; p < npass; ++p) {
+                const int c0 = (p * 64 + lane) * 4;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (c0 + 3 < nch) v = *reinterpret_cast<const f32x4*>(row + c0);
+                else
+                    for (int e = 0; e < 4; ++e)
+                        if (c0 + e < nch) v[e] = row[c0 + e];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = c0 + e;
+                    const int k = c / a.K, cls = c - k * a.K - 5;
+                    const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
+                    if (c < nch && cls >= 0 && o > k_.thr) {
+                        const float s = __fmul_rn(sigmoid_acc(v[e]), o);
+                        BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
+                        if (best_before(s, cls, b)) b = BestClass{s, cls};
+                    }
+                }
+            }
+            int cnt = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (!(obj[k] > k_.thr)) continue;
+                BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) {
+                    const BestClass t = {__shfl_xor(b.s, d, 64), __shfl_xor(b.c, d, 64)};
+                    if (best_before(t.s, t.c, b)) b = t;
+                }
+                if (b.c != 0x7fffffff && b.s > k_.thr && (k_.cmask == nullptr || class_allowed(k_.cmask, b.c))) {
+                    if (lane == 0) {
+                        const int anchor = a.level_off + (k * a.h + y) * a.w + x;
+                        bhi[fill + cnt] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(b.s));
+                        blo[fill + cnt] = ((unsigned)anchor << k_.label_bits) | (unsigned)b.c;
+                    }
+                    ++cnt;
+                }
+            }
+            fill += cnt;
+            continue;
+        }
+        for (int p = 0; p < npass; ++p) {
+            const int c0 = (p * 64 + lane) * 4;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (c0 + 3 < nch) v = *reinterpret_cast<const f32x4*>(row + c0);
+            else
+                for (int e = 0; e < 4; ++e)
+                    if (c0 + e < nch) v[e] = row[c0 + e];
+            float sc[4];
+            unsigned cand[4];
+            int cnt = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = c0 + e;
+                const int k = c / a.K, cls = c - k * a.K - 5;
+                bool ok = (c < nch) && (cls >= 0);
+                float s = 0.f;
+                if (ok) {
+                    const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
+                    s = __fmul_rn(sigmoid_acc(v[e]), o);
+                    ok = s > k_.thr;
+                    if (k_.cmask != nullptr) ok = ok && class_allowed(k_.cmask, cls);
+                }
+                sc[e] = s;
+                const int anchor = a.level_off + (k * a.h + y) * a.w + x;
+                cand[e] = ((unsigned)anchor << k_.label_bits) | (unsigned)(cls < 0 ? 0 : cls);
+                if (!ok) cand[e] = 0xffffffffu;
+                cnt += ok ? 1 : 0;
+            }
+            int incl = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += t;
+            }
+            const int total = __shfl(incl, 63, 64);
+            if (total == 0) continue;
+            if (fill + total > DEC_BUF) flush();
+            int pos = fill + incl - cnt;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (cand[e] != 0xffffffffu) {
+                    if (pos < DEC_BUF) {
+                        bhi[pos] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(sc[e]));
+                        blo[pos] = cand[e];
+                    }
+                    ++pos;
+                }
+            }
+            fill += total;
+            if (fill > DEC_BUF) fill = DEC_BUF;
+        }
+    }
+    flush();
+}
+
 __global__ void finalize_count_kernel(int* status, int cap) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (status[ST_NCAND] > cap) status[ST_OVERFLOW] = 1;
@@ -1852,6 +2020,44 @@ static int post_decode_launch(const ymi_post_desc* d, hipStream_t s) {
     return check_launch("decode_kernel");
 }
 
+// stage 2 of 3, augmented inference: decode + threshold of one view's fp32 head outputs into its range of the sink's concatenated anchor axis
+int post_decode_view_launch(const ymi_post_desc* d, const ymi_post_view* v, hipStream_t s) {
+    YMI_REQUIRE(v != nullptr, "ymi_post_decode_view: null view");
+    PostLayout L;
+    Workspace w;
+    int rc = post_validate(d, false, L, w);
+    if (rc != YMI_OK) return rc;
+    YMI_REQUIRE(v->num_levels >= 1 && v->num_levels <= YMI_MAX_LEVELS, "ymi_post_decode_view: num_levels %d out of range", v->num_levels);
+    YMI_REQUIRE(v->scale > 0.f && v->scale <= 1.f, "ymi_post_decode_view: scale %g outside (0, 1]", (double)v->scale);
+    YMI_REQUIRE(v->flip_w >= 0 && v->flip_w < (1 << 24), "ymi_post_decode_view: flip_w %d out of range", v->flip_w);
+    YMI_REQUIRE(v->anchor_base >= 0 && (v->skip_mask >> v->num_levels) == 0, "ymi_post_decode_view: negative anchor_base / skip_mask names a level the view does not have");
+    int64_t kept = 0;
+    for (int l = 0; l < v->num_levels; ++l) {
+        if ((v->skip_mask >> l) & 1) continue;
+        YMI_REQUIRE(v->lh[l] >= 1 && v->lw[l] >= 1, "ymi_post_decode_view: level %d has an empty grid", l);
+        YMI_REQUIRE(v->logits[l] != nullptr, "ymi_post_decode_view: logits[%d] is null", l);
+        YMI_REQUIRE(v->lcstride[l] >= 3 * (d->num_classes + 5) && v->lcstride[l] % 4 == 0, "ymi_post_decode_view: lcstride[%d]=%d too small / not a multiple of 4", l, v->lcstride[l]);
+        kept += (int64_t)3 * v->lh[l] * v->lw[l];
+    }
+    YMI_REQUIRE((int64_t)v->anchor_base + kept <= L.total_anchors, "ymi_post_decode_view: anchors [%d, %lld) of the view exceed the sink's %d", v->anchor_base,
+                (long long)(v->anchor_base + kept), L.total_anchors);
+    int level_off = v->anchor_base;
+    for (int l = 0; l < v->num_levels; ++l) {
+        if ((v->skip_mask >> l) & 1) continue;   // a clipped tail: no launch, no anchor indices
+        DecodeViewArgs va;
+        DecodeArgs& a = va.d;
+        a.logits = v->logits[l]; a.h = v->lh[l]; a.w = v->lw[l]; a.cs = v->lcstride[l]; a.stride = v->stride[l];
+        for (int k = 0; k < 6; ++k) a.anc[k] = v->anchors[l][k];
+        a.n = d->n; a.K = d->num_classes + 5; a.level_off = level_off;
+        a.sink = make_sink(d, w, L);
+        va.scale = v->scale; va.flip_w = (float)v->flip_w;
+        const int64_t npix = (int64_t)d->n * a.h * a.w;
+        hipLaunchKernelGGL(decode_view_kernel, dim3((unsigned)((npix + 4 * DEC_PIX_PER_WAVE - 1) / (4 * DEC_PIX_PER_WAVE))), dim3(256), 0, s, va);
+        level_off += 3 * a.h * a.w;
+    }
+    return check_launch("decode_view_kernel");
+}
+
 // stage 3 of 3: sort, class-aware NMS, top-k + rescale, from the records the producers appended
 int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
     PostLayout L;
@@ -1990,6 +2196,7 @@ extern "C" int ymi_post_set_classes(const ymi_post_desc* d, const int32_t* class
 extern "C" int ymi_postprocess(const ymi_post_desc* d, void* stream) { return postprocess_launch(d, (hipStream_t)stream); }
 extern "C" int ymi_post_begin(const ymi_post_desc* d, void* stream) { return post_begin_launch(d, (hipStream_t)stream); }
 extern "C" int ymi_post_finish(const ymi_post_desc* d, void* stream) { return post_finish_launch(d, (hipStream_t)stream); }
+extern "C" int ymi_post_decode_view(const ymi_post_desc* sink, const ymi_post_view* view, void* stream) { return post_decode_view_launch(sink, view, (hipStream_t)stream); }
 
 extern "C" int64_t ymi_nms_ws_bytes(int n) {
     if (n <= 0) n = 1;

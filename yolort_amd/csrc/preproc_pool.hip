@@ -81,6 +81,69 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const LetterboxArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// View canvas of augmented inference (ymi_scale_view): the letterboxed NHWC4 canvas scaled (and mirrored left-right) into a
+// smaller NHWC4 canvas.  Replaces yolort/v5/utils/torch_utils.py:288-300 (scale_img: F.interpolate bilinear, align_corners=False,
+// then F.pad with 0.447) and the x.flip(3) of yolort/v5/models/yolo.py:158.  ATen's upsample_bilinear2d arithmetic as its CPU kernel evaluates it: the source index
+// scale * (dst + 0.5) - 0.5 is ONE fused multiply-add (a single rounding of the exact expression), the four taps carry the products of the row and column weights,
+// w_ij = fl(h_i * w_j), and the value is the chain fma(w11, v11, fma(w10, v10, fma(w00, v00, fl(w01 * v01)))) -- five roundings in all, and bit-identical to
+// F.interpolate wherever the weights are powers of two (ratio 0.5).  The nested form h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) differs from it by an ulp.
+// HBM-bound: one thread per DESTINATION pixel, whole pixels move as one 8-byte (16-bit types) or 16-byte (fp32) access -- the stores
+// of a wave are one contiguous run, its four taps read two source rows at a stride of in / out (< 2) pixels.  The mirror costs an
+// index subtraction: column x reads source column w - 1 - x (flip first, then scale).
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(256) void scale_view_kernel(const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip) {
+    const int64_t npix = (int64_t)dh * dw;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= npix * n) return;
+    const int img = (int)(gid / npix);
+    const int rem = (int)(gid - (int64_t)img * npix);
+    const int y = rem / dw, x = rem - y * dw;
+    float v[3] = {YMI_VIEW_PAD, YMI_VIEW_PAD, YMI_VIEW_PAD};
+    if (y < sh && x < sw) {
+        const float sy = (float)h / (float)sh, sx = (float)w / (float)sw;
+        float fy = fmaf(sy, (float)y + 0.5f, -0.5f);
+        float fx = fmaf(sx, (float)x + 0.5f, -0.5f);
+        fy = fy < 0.f ? 0.f : fy;
+        fx = fx < 0.f ? 0.f : fx;
+        int y0 = (int)fy, x0 = (int)fx;
+        y0 = y0 > h - 1 ? h - 1 : y0;
+        x0 = x0 > w - 1 ? w - 1 : x0;
+        const int y1 = y0 + 1 > h - 1 ? h - 1 : y0 + 1;
+        int x1 = x0 + 1 > w - 1 ? w - 1 : x0 + 1;
+        float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
+        ly1 = ly1 < 0.f ? 0.f : (ly1 > 1.f ? 1.f : ly1);
+        lx1 = lx1 < 0.f ? 0.f : (lx1 > 1.f ? 1.f : lx1);
+        const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+        if (flip) { x0 = w - 1 - x0; x1 = w - 1 - x1; }   // both stay inside [0, w)
+        const int64_t r0 = ((int64_t)img * h + y0) * w, r1 = ((int64_t)img * h + y1) * w;
+        float p00[3], p01[3], p10[3], p11[3];
+        auto load = [&](int64_t pix, float* p) {
+            if constexpr (DT == YMI_F32) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>((const float*)src + pix * 4);
+                p[0] = t[0]; p[1] = t[1]; p[2] = t[2];
+            } else {
+                const u32x2 t = *reinterpret_cast<const u32x2*>((const uint16_t*)src + pix * 4);
+                p[0] = from16<DT>((uint16_t)(t[0] & 0xffff)); p[1] = from16<DT>((uint16_t)(t[0] >> 16)); p[2] = from16<DT>((uint16_t)(t[1] & 0xffff));
+            }
+        };
+        load(r0 + x0, p00); load(r0 + x1, p01); load(r1 + x0, p10); load(r1 + x1, p11);
+        const float w00 = __fmul_rn(ly0, lx0), w01 = __fmul_rn(ly0, lx1), w10 = __fmul_rn(ly1, lx0), w11 = __fmul_rn(ly1, lx1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = fmaf(w11, p11[c], fmaf(w10, p10[c], fmaf(w00, p00[c], __fmul_rn(w01, p01[c]))));
+    }
+    if constexpr (DT == YMI_F32) {
+        const f32x4 o = {v[0], v[1], v[2], 0.f};
+        *reinterpret_cast<f32x4*>((float*)dst + gid * 4) = o;
+    } else {
+        u32x2 o;
+        o[0] = (uint32_t)to16<DT>(v[0]) | ((uint32_t)to16<DT>(v[1]) << 16);
+        o[1] = (uint32_t)to16<DT>(v[2]);
+        *reinterpret_cast<u32x2*>((uint16_t*)dst + gid * 4) = o;
+    }
+}
+
 // Identity-size fast path (every image already has its resized size, the fixed-size stream case):
 // the bilinear weights are exactly (1,0), so the result equals the source pixel bit for bit and the
 // kernel degenerates into a planar-CHW -> NHWC4 interleave.  Four pixels per thread: one 8-byte load
@@ -954,4 +1017,20 @@ extern "C" int ymi_copy_view(const void* x, int x_cstride, int npix, int c, void
     dim3 grid((unsigned)((total + 255) / 256)), block(256);
     hipLaunchKernelGGL(copy_view_kernel, grid, block, 0, (hipStream_t)stream, (const uint16_t*)x, x_cstride, (int64_t)npix, c, (uint16_t*)y, y_cstride);
     return check_launch("copy_view_kernel");
+}
+
+extern "C" int ymi_scale_view(const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype, void* stream) {
+    YMI_REQUIRE(src && dst && src != dst, "ymi_scale_view: null buffer / in place");
+    YMI_REQUIRE(n >= 0 && h >= 1 && w >= 1 && dh >= 1 && dw >= 1, "ymi_scale_view: empty canvas (%d x %d -> %d x %d)", h, w, dh, dw);
+    YMI_REQUIRE(sh >= 1 && sw >= 1 && sh <= dh && sw <= dw, "ymi_scale_view: resized size %d x %d does not fit the %d x %d destination", sh, sw, dh, dw);
+    YMI_REQUIRE(dtype == YMI_F16 || dtype == YMI_BF16 || dtype == YMI_F32, "ymi_scale_view: dtype must be F16/BF16/F32");
+    const int64_t total = (int64_t)n * dh * dw;
+    if (total == 0) return YMI_OK;
+    YMI_REQUIRE((total + 255) / 256 < ((int64_t)1 << 31), "ymi_scale_view: destination too large");
+    dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == YMI_F32) hipLaunchKernelGGL((scale_view_kernel<YMI_F32>), grid, block, 0, s, src, n, h, w, dst, dh, dw, sh, sw, flip);
+    else if (dtype == YMI_F16) hipLaunchKernelGGL((scale_view_kernel<YMI_F16>), grid, block, 0, s, src, n, h, w, dst, dh, dw, sh, sw, flip);
+    else hipLaunchKernelGGL((scale_view_kernel<YMI_BF16>), grid, block, 0, s, src, n, h, w, dst, dh, dw, sh, sw, flip);
+    return check_launch("scale_view_kernel");
 }

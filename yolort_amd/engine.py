@@ -727,6 +727,51 @@ class Plan:
     def post_finish(self, d: PostDesc, total_anchors: int) -> None:
         self._record(self.lib.ymi_plan_add_post_finish(self.handle, C.byref(d)), "postprocess", kind="post", flops=0.0, bytes=0.0, shape=f"A={total_anchors}")
 
+    # augmented inference (include/yolort_amd.h ymi_scale_view / ymi_post_decode_view): view canvases and one candidate producer per view
+    def scale_view(self, x: View, ratio: float, flip: bool, gs: int, name: str = "scale_view") -> View:
+        """a new NHWC4 canvas holding `x` (the letterboxed NHWC4 canvas) scaled by `ratio`, mirrored left-right first when `flip` (scale_img + x.flip(3))"""
+        if x.c != 4 or x.cs != 4:
+            raise YmiError(f"{name}: the source must be a dense NHWC4 canvas")
+        (sh, sw), (dh, dw) = _lib.tta_view_size(x.h, x.w, ratio, gs)
+        out = self.alloc(x.n, dh, dw, 4, x.dtype, zero=True)
+        esz = x.base.element_size()
+        self._record(self.lib.ymi_plan_add_scale_view(self.handle, x.ptr, x.n, x.h, x.w, out.ptr, dh, dw, sh, sw, 1 if flip else 0, dtype_code(x.dtype)), name,
+                     kind="copy", flops=0.0, bytes=float(x.n * (x.h * x.w + dh * dw) * 4 * esz), shape=f"{x.h}x{x.w} -> {sh}x{sw} in {dh}x{dw}{' mirrored' if flip else ''}")
+        return out
+
+    @staticmethod
+    def post_view(logits: Sequence[View], strides: Sequence[float], anchors: Sequence[Sequence[float]], skip_mask: int, anchor_base: int, scale: float, flip_w: int) -> "_lib.PostView":
+        v = _lib.PostView()
+        for i, lv in enumerate(logits):
+            if lv.dtype != torch.float32:
+                raise YmiError("post-process expects fp32 head logits")
+            v.logits[i], v.lh[i], v.lw[i], v.lcstride[i] = lv.ptr, lv.h, lv.w, lv.cs
+            v.stride[i] = float(strides[i])
+            for k in range(6):
+                v.anchors[i][k] = float(anchors[i][k])
+        v.num_levels, v.skip_mask, v.anchor_base, v.scale, v.flip_w = len(logits), skip_mask, anchor_base, float(scale), int(flip_w)
+        return v
+
+    def post_decode_view(self, d: PostDesc, v: "_lib.PostView", name: str = "decode_view") -> None:
+        kept = [l for l in range(v.num_levels) if not (v.skip_mask >> l) & 1]
+        self._record(self.lib.ymi_plan_add_post_decode_view(self.handle, C.byref(d), C.byref(v)), name, kind="post", flops=0.0,
+                     bytes=float(sum(d.n * v.lh[l] * v.lw[l] * 3 * (d.num_classes + 5) * 4 for l in kept)), shape=f"scale {v.scale:.2f} base {v.anchor_base} levels {kept}")
+
+    def postprocess_tta(self, view_logits: Sequence[Sequence[View]], scales: Sequence[float], flips: Sequence[bool], canvas_w: int, strides: Sequence[float],
+                        anchors: Sequence[Sequence[float]], num_classes: int, score_thresh: float, nms_thresh: float, detections_per_img: int, cand_cap: int,
+                        rescale: Optional[Tensor] = None, flags: int = 0, classes: Optional[Sequence[int]] = None) -> "PostBuffers":
+        """post_begin, one ymi_post_decode_view per view (stored fp32 logits), post_finish: the post-process of augmented inference over the concatenated anchor axis of
+        the views without their tails (_lib.tta_layout).  The last op (post_finish) is the side-stream range, as with the fused head."""
+        n = view_logits[0][0].n
+        layout, total = _lib.tta_layout([[(v.h, v.w) for v in lv] for lv in view_logits])
+        pb, d = self.post_desc([(1, total // 3)], n, [1.0], [[0.0] * 6], num_classes, score_thresh, nms_thresh, detections_per_img, cand_cap, rescale, flags=flags, classes=classes)
+        self.post_begin(d)
+        for vi, lv in enumerate(view_logits):
+            skip, base = layout[vi]
+            self.post_decode_view(d, self.post_view(lv, strides, anchors, skip, base, scales[vi], canvas_w if flips[vi] else 0), name=f"decode_view.{vi}")
+        self.post_finish(d, total)
+        return pb
+
     def stem_from_planar(self, images: Sequence[Tensor], stream: Optional[torch.cuda.Stream] = None, ptrs: Optional[bytes] = None) -> int:
         """op 0 (the stem conv in super-pixel form) computed straight from planar (3, H, W) images of the compute dtype:
         identity-size batches skip the letterbox pass and its NHWC4 round trip (ymi_conv_stem_planar).  When op 1 is

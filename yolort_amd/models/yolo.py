@@ -14,7 +14,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor, nn
 
-from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_CLASS_FILTER, POST_EXACT_FULL, YmiError, check, merge_flags, normalize_classes
+from .._lib import POST_AGNOSTIC, POST_BEST_CLASS, POST_CLASS_FILTER, POST_EXACT_FULL, TTA_FLIPS, TTA_SCALES, YmiError, check, merge_flags, normalize_classes
 from ..engine import Plan, View
 from ..hipmodule import compute_dtype_of, nchw_to_view, view_to_nchw, weights_signature
 from ..ops import slab_to_list
@@ -181,6 +181,7 @@ class YOLO(nn.Module):
         classes: Optional[Sequence[int]] = None,
         merge: bool = False,
         merge_redundant: bool = True,
+        augment: bool = False,
     ):
         super().__init__()
         if not hasattr(backbone, "out_channels"):
@@ -203,6 +204,15 @@ class YOLO(nn.Module):
             raise ValueError("merge= / merge_redundant= configure the package's own PostProcess: with an injected post_process, set the attributes on that module")
         elif classes is not None:   # an injected module is taken as it is: a set given next to it would be dropped without a word
             raise ValueError("classes= configures the package's own PostProcess: with an injected post_process, set the filter on that module")
+        # Augmented inference (test-time augmentation; ultralytics' DetectionModel.forward(x, augment=True) -> _forward_augment, yolort/v5/models/yolo.py:147-163, what
+        # AutoShape.forward(imgs, size, augment) exposes): the letterboxed batch runs at scale 1, at 0.83 mirrored left-right and at 0.67, the predictions of the smaller
+        # views are brought back to the full canvas, the three sets are concatenated without their tails and ONE NMS runs over the union -- all inside one recorded plan
+        # (_build_entry).  A live attribute like post_process.agnostic: flipping it selects another plan on the next batch.  Needs the package's own head, anchor
+        # generator and post-process, and a canvas whose sides are multiples of the largest stride (_augment_check).
+        self.augment = bool(augment)
+        if self.augment and not self.fused():
+            raise ValueError("augment=True needs the package's own head, anchor generator and post-process (the views are decoded by the fused post-process); "
+                             "an injected head / anchor_generator / post_process cannot be augmented")
         self.compute_dtype = torch.float16  # used when parameters are fp32 (see hipmodule.compute_dtype_of)
         # the conv stack of a batch is replayed as ONE captured hipGraph launch (csrc/api.cpp ymi_plan_run: captured once per plan instance and op range) instead of ~45
         # kernel launches from the host: same kernels, same order, same results (tests/test_boundary_gpu.py), 0.12 ms less host time per batch (profiles/r04n_pipeline_depth_graph.txt).
@@ -305,7 +315,18 @@ class YOLO(nn.Module):
         key = (pp.score_thresh, pp.nms_thresh, pp.detections_per_img, bool(getattr(pp, "multi_label", True)), bool(getattr(pp, "agnostic", False)))
         key = key if classes is None else key + (True,)   # (the key of a model without a filter is the one it always was)
         mf = merge_flags(bool(getattr(pp, "merge", False)), bool(getattr(pp, "merge_redundant", True)))
-        return key + (("merge", mf),) if mf else key   # (... and so is the key of a model without merge-NMS; the element is a pair: never the filter's True)
+        key = key + (("merge", mf),) if mf else key   # (... and so is the key of a model without merge-NMS; the element is a pair: never the filter's True)
+        return key + (("augment", True),) if getattr(self, "augment", False) else key   # (... and of a model without augmented inference)
+
+    def _augment_check(self, h: int, w: int) -> None:
+        """augmented inference: what has to hold for an (h, w) canvas -- ValueError otherwise, before anything is allocated or recorded"""
+        if not self.fused():
+            raise ValueError("augment=True needs the package's own head, anchor generator and post-process (the views are decoded by the fused post-process); "
+                             "an injected head / anchor_generator / post_process cannot be augmented")
+        gs = int(max(self.anchor_generator.strides))
+        if h % gs or w % gs:
+            raise ValueError(f"augment=True needs a canvas whose sides are multiples of the largest stride {gs} (the clipped tails of the views are whole pyramid levels "
+                             f"only then); got {h} x {w}: letterbox with size_divisible={gs} or pad the batch")
 
     def _entry(self, n: int, h: int, w: int, device: torch.device, classes=_LIVE) -> _PlanEntry:
         """a plan instance of this shape whose previous batch has been collected by the host.  Instances are built lazily
@@ -316,6 +337,8 @@ class YOLO(nn.Module):
         canvases without rebuilding plans."""
         cdt = compute_dtype_of(self)
         pp = self.post_process
+        if getattr(self, "augment", False):
+            self._augment_check(h, w)
         post_key = self._post_key(classes)
 
         base = (n, h, w, cdt, device.index, self._frozen_signature if self._frozen_signature is not None else weights_signature(self), post_key)   # (walks every parameter: once per submission, the host side of a step is ~0.3 ms)
@@ -387,6 +410,21 @@ class YOLO(nn.Module):
             strides = [float(s) for s in ag.strides]
             args = (self.num_classes, float(pp.score_thresh), float(pp.nms_thresh), int(pp.detections_per_img), self.cand_cap_per_image * n)
             flags = (POST_EXACT_FULL if self.post_exact_full else 0) | (0 if getattr(pp, "multi_label", True) else POST_BEST_CLASS) | (POST_AGNOSTIC if getattr(pp, "agnostic", False) else 0) | (POST_CLASS_FILTER if self._classes(classes) is not None else 0) | merge_flags(bool(getattr(pp, "merge", False)), bool(getattr(pp, "merge_redundant", True)))   # rebuilt plans (capacity growth, exact full pass) come through here too
+            if getattr(self, "augment", False):
+                # Augmented inference: views 1 and 2 are made from the canvas by the scale kernel, every view runs the backbone and the head (stored fp32 logits: a
+                # fused-head twin of the view decode is future work) on this same plan, and one post-process takes the three candidate sets.
+                # Ops: [backbone + head of view 0 | scale, backbone, head of view 1 | ... view 2 | post_begin, three view decodes] on the main stream, post_finish on
+                # the side stream -- the op ranges, graph capture, ring, capacity / exact-full rebuilds and the class-set rewrite are the ones of every other plan.
+                gs = int(max(ag.strides))
+                view_logits = [self.head.emit(plan, feats)]
+                for ratio, flip in zip(TTA_SCALES[1:], TTA_FLIPS[1:]):
+                    xv = plan.scale_view(x, ratio, flip, gs, name=f"scale_view.{ratio}")
+                    view_logits.append(self.head.emit(plan, self.backbone.emit(plan, xv)))
+                logits = view_logits[0]
+                post = plan.postprocess_tta(view_logits, TTA_SCALES, TTA_FLIPS, w, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
+                entry = _PlanEntry(plan, x, feats, logits, post, rescale, n_backbone)
+                entry.view_logits = view_logits
+                return entry
             if self.fuse_head_decode and self.head.can_fuse_decode(plan, feats):
                 post, pd = plan.post_desc([(f.h, f.w) for f in feats], n, strides, ag.anchor_grids, *args, rescale=rescale, flags=flags)
                 plan.post_begin(pd)
@@ -565,7 +603,7 @@ class YOLO(nn.Module):
     @classmethod
     def load_from_yolov5(cls, checkpoint_path: str, score_thresh: float = 0.25, nms_thresh: float = 0.45, version: str = "r6.0",
                          post_process: Optional[nn.Module] = None, multi_label: bool = True, agnostic: bool = False, classes: Optional[Sequence[int]] = None,
-                         merge: bool = False, merge_redundant: bool = True):
+                         merge: bool = False, merge_redundant: bool = True, augment: bool = False):
         """Load model state from a checkpoint trained by ultralytics/yolov5 (reference yolo.py:185-223)."""
         from ._checkpoint import load_from_ultralytics
 
@@ -573,7 +611,7 @@ class YOLO(nn.Module):
         backbone_name = f"darknet_{info['size']}_{version.replace('.', '_')}"
         backbone = darknet_pan_backbone(backbone_name, info["depth_multiple"], info["width_multiple"], version=version, use_p6=info["use_p6"])
         model = cls(backbone, info["num_classes"], strides=info["strides"], anchor_grids=info["anchor_grids"], score_thresh=score_thresh,
-                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic, classes=classes, merge=merge, merge_redundant=merge_redundant)
+                    nms_thresh=nms_thresh, post_process=post_process, multi_label=multi_label, agnostic=agnostic, classes=classes, merge=merge, merge_redundant=merge_redundant, augment=augment)
         model.load_state_dict(info["state_dict"])
         return model
 

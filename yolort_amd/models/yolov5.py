@@ -120,7 +120,8 @@ class YOLOv5(nn.Module):
         main = e.main_stream   # every launch below names its stream: no stream context is entered on the default path
         # fixed-size stream: every image already is the canvas (resize = identity, no padding) in the compute dtype ->
         # the stem reads the planar images itself, the letterbox pass and its NHWC4 copy are skipped (bit-identical)
-        planar = model.stem_from_planar and identity and e.plan.stem_planar_ok(images, (hb, wb), scan)
+        # (not under augmented inference: the canvas itself is the source of the smaller views, so it has to be filled)
+        planar = model.stem_from_planar and not getattr(model, "augment", False) and identity and e.plan.stem_planar_ok(images, (hb, wb), scan)
         ev0 = None
         first_op = 0
         ptrs = None

@@ -111,3 +111,73 @@ def postprocess_logits(head_outputs: Sequence[Tensor], strides: Sequence[float],
         cap = n * (1 << ((cap + n - 1) // n - 1).bit_length())   # per-image regions are powers of two
     counts = pb.count.cpu().tolist()
     return slab_to_list(pb.boxes, pb.scores, pb.labels, counts)
+
+
+def scale_image(x: Tensor, ratio: float, flip: bool = False, gs: int = 32) -> Tensor:
+    """A view of augmented inference: (n, 3, h, w) -> (n, 3, H', W'), `x` mirrored left-right first when `flip`, resized by `ratio` with F.interpolate's bilinear
+    arithmetic (align_corners=False) and padded with 0.447 to the next multiples of `gs` -- scale_img of yolort/v5/utils/torch_utils.py:288-300 plus the x.flip(3) of
+    yolort/v5/models/yolo.py:158, as one kernel over the NHWC4 canvas (ymi_scale_view).  fp16 / bf16 / fp32; ratio 1.0 returns a copy (mirrored when `flip`:
+    every bilinear weight is then exactly 1)."""
+    lib = _lib.load(require_gpu=True)
+    if not x.is_cuda or x.dim() != 4 or x.shape[1] != 3:
+        raise YmiError("scale_image takes an (n, 3, h, w) tensor on an MI355X (no CPU fallback)")
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError(f"scale_image: ratio {ratio} outside (0, 1]")
+    n, _, h, w = x.shape
+    dt = _lib.dtype_code(x.dtype)
+    (sh, sw), (dh, dw) = _lib.tta_view_size(h, w, ratio, gs)
+    if sh < 1 or sw < 1:
+        raise ValueError(f"scale_image: {h} x {w} at ratio {ratio} leaves no pixel")
+    src = torch.zeros(n, h, w, 4, device=x.device, dtype=x.dtype)
+    src[..., :3] = x.permute(0, 2, 3, 1)
+    dst = torch.empty(n, dh, dw, 4, device=x.device, dtype=x.dtype)
+    check(lib.ymi_scale_view(src.data_ptr(), n, h, w, dst.data_ptr(), dh, dw, sh, sw, 1 if flip else 0, dt, _lib.stream_ptr()), "ymi_scale_view")
+    return dst[..., :3].permute(0, 3, 1, 2).contiguous()
+
+
+def postprocess_logits_tta(view_outputs: Sequence[Sequence[Tensor]], scales: Sequence[float], flips: Sequence[bool], canvas_hw: Sequence[int], strides: Sequence[float],
+                           anchors: Sequence[Sequence[float]], num_classes: int, score_thresh: float, nms_thresh: float, detections_per_img: int,
+                           cand_cap: Optional[int] = None, multi_label: bool = True, agnostic: bool = False, classes: Optional[Sequence[int]] = None, merge: bool = False,
+                           merge_redundant: bool = True) -> List[Dict[str, Tensor]]:
+    """The post-process of augmented inference (ultralytics' _forward_augment, yolort/v5/models/yolo.py:152-163) on reference-layout head outputs: view_outputs[v] =
+    [(N, 3, H, W, K)] per level of view v (the model's outputs on the view canvas of scale scales[v], mirrored left-right when flips[v]); canvas_hw = the full canvas.
+    Every view is decoded, its boxes are brought back to the full canvas (/ scale, W - x for a mirrored view), view 0 loses its coarsest level and the last view its
+    finest, and ONE NMS runs over the union (ymi_post_begin, ymi_post_decode_view per view, ymi_post_finish).  The keyword arguments are postprocess_logits's."""
+    classes = _lib.normalize_classes(classes, num_classes)
+    _lib.load(require_gpu=True)
+    if len(view_outputs) != len(scales) or len(scales) != len(flips) or not view_outputs:
+        raise ValueError("postprocess_logits_tta: one scale and one flip per view")
+    h0 = view_outputs[0][0]
+    if not h0.is_cuda:
+        raise YmiError("postprocess runs on an MI355X only (no CPU fallback)")
+    n = h0.shape[0]
+    k = num_classes + 5
+    cs = (3 * k + 3) // 4 * 4
+    plan_inputs = []
+    for outs in view_outputs:
+        lv = []
+        for ho in outs:
+            if ho.shape[0] != n or ho.shape[1] != 3 or ho.shape[-1] != k:
+                raise YmiError(f"expected ({n},3,H,W,{k}) head outputs, got {tuple(ho.shape)}")
+            nhwc = torch.zeros(n, ho.shape[2], ho.shape[3], cs, device=ho.device, dtype=torch.float32)
+            nhwc[..., : 3 * k] = ho.to(torch.float32).permute(0, 2, 3, 1, 4).reshape(n, ho.shape[2], ho.shape[3], 3 * k)
+            lv.append(nhwc)
+        plan_inputs.append(lv)
+    cap = cand_cap or max(4096, 2048 * n)
+    flags = (0 if multi_label else _lib.POST_BEST_CLASS) | (_lib.POST_AGNOSTIC if agnostic else 0) | _lib.merge_flags(merge, merge_redundant)
+    while True:
+        plan = Plan(h0.device, torch.float16)
+        views = [[View(t.view(-1), 0, n, t.shape[1], t.shape[2], 3 * k, t.shape[3]) for t in lv] for lv in plan_inputs]
+        pb = plan.postprocess_tta(views, scales, flips, int(canvas_hw[1]), strides, anchors, num_classes, score_thresh, nms_thresh, detections_per_img, cap, flags=flags, classes=classes)
+        plan.run()
+        st = pb.status.cpu().tolist()
+        if st[1] == 0:
+            break
+        if not st[1] & 1:
+            flags |= _lib.POST_EXACT_FULL
+            continue
+        need = max(st[0], st[3] * n)
+        cap = max(int(need * 1.25) + 1024, 2 * cap)
+        cap = n * (1 << ((cap + n - 1) // n - 1).bit_length())
+    counts = pb.count.cpu().tolist()
+    return slab_to_list(pb.boxes, pb.scores, pb.labels, counts)
