@@ -214,6 +214,38 @@ def _view_decode_case(lib, nc, mode, device):
     return seen
 
 
+ONE_BODY_PARAMS = ((3, 0.3), (171, 0.0))   # (num_classes, score_thresh); 171 classes at a threshold <= 0: 3 * 171 = 513 records per pixel > DEC_BUF = 512, the flush in mid-pixel
+ONE_BODY_MODES = {"multi": (0, False), "multi-filter": (0, True), "best": (T.POST_BEST_CLASS, False), "best-filter": (T.POST_BEST_CLASS, True)}
+ONE_BODY_CAP = 2 * 16384                   # per image more than the 63 * 171 = 10773 records of the second parameter set
+
+
+def _one_body_case(lib, nc, thr, mode, device):
+    """decode_kernel and decode_view_kernel are two entry points of ONE body: ymi_post_begin, one ymi_post_decode_view with scale 1, no mirror, anchor base 0 and no
+    skipped level, ymi_post_finish == ymi_postprocess of the same logits BIT FOR BIT in boxes, scores, labels, counts and all status words (a division by 1.0 is exact).
+    Two images over levels of 4 x 4, 2 x 2 and 1 x 1: a wave walks 8 pixels, so in the two coarse levels (8 and 2 pixels in all) the image changes inside a wave."""
+    import _post_cases
+    flags, filtered = ONE_BODY_MODES[mode]
+    classes = None if not filtered else ((0, 2) if nc == 3 else (0, 3, 17, 41, 79, 170))
+    flags |= T.POST_CLASS_FILTER if filtered else 0
+    n, k = 2, 300
+    heads = _post_cases.post_heads(nc, [(4, 4), (2, 2), (1, 1)], n=n, seed=23)
+    plain = T.run_views(lib, [dict(heads=heads)], n, nc, STRIDES3, ANCH3, thr, 0.45, k, ONE_BODY_CAP, flags, classes, device, plain=True)
+    view = T.run_views(lib, [dict(heads=heads, scale=1.0, flip_w=0, base=0, skip=0)], n, nc, STRIDES3, ANCH3, thr, 0.45, k, ONE_BODY_CAP, flags, classes, device)
+    print(f"nc {nc} thr {thr} {mode}: status {plain['status'].tolist()} counts {plain['count'].tolist()}")
+    assert int(plain["status"][1]) == 0 and int(plain["count"].min()) > 0
+    if nc == 171 and mode == "multi":
+        assert int(plain["status"][4]) == n * 63 * 171   # every (anchor, class) pair of every pixel: 513 records per pixel
+    for key in ("boxes", "scores", "labels", "count", "status"):
+        assert torch.equal(view[key], plain[key]), key
+    return plain
+
+
+@pytest.mark.parametrize("mode", list(ONE_BODY_MODES))
+@pytest.mark.parametrize("nc,thr", ONE_BODY_PARAMS)
+def test_scale1_view_decode_equals_the_plain_decode_bit_for_bit_on_the_simulator(sim, nc, thr, mode):
+    _one_body_case(sim, nc, thr, mode, "cpu")
+
+
 def _union_case(lib, nc, flags, classes, device, strides=STRIDES3, anchors=ANCH3, hw=T.CANVAS):
     """three views with their tails clipped, nms_thresh 1.0: every candidate comes out, in the order of torch.cat(y, 1) under a stable sort by score"""
     shapes = T.view_shapes(*hw, strides)

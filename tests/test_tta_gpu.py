@@ -62,6 +62,12 @@ def test_view_decode_equals_the_transformed_scale1_decode(dev, lib, nc, mode):
     CPU._view_decode_case(lib, nc, mode, dev)
 
 
+@pytest.mark.parametrize("mode", list(CPU.ONE_BODY_MODES))
+@pytest.mark.parametrize("nc,thr", CPU.ONE_BODY_PARAMS)
+def test_scale1_view_decode_equals_the_plain_decode_bit_for_bit(dev, lib, nc, thr, mode):
+    CPU._one_body_case(lib, nc, thr, mode, dev)
+
+
 @pytest.mark.parametrize("flags,classes", [(0, None), (T.POST_BEST_CLASS, None), (T.POST_CLASS_FILTER, (1,))], ids=["multi", "best", "filter"])
 def test_three_views_anchor_bases_and_tie_order(dev, lib, sim, flags, classes):
     """... and the integer outputs (counts, labels, status words) equal the simulator's run of the same inputs; so do scores and boxes of these exact-palette inputs"""

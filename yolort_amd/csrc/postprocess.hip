@@ -60,12 +60,25 @@ struct DecodeArgs {
 constexpr int DEC_PIX_PER_WAVE = 8;     // pixels walked by one wave
 constexpr int DEC_BUF = 512;            // candidate records buffered per wave in LDS before ONE global atomic
 
-__global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
+// a view's box back on the full canvas (_descale_pred, yolo.py:181-197): y' = y / scale, x' = x / scale, or mirrored x1' = W - x2 / scale, x2' = W - x1 / scale; every
+// operation an explicitly rounded fp32 one
+__device__ __forceinline__ f32x4 descale_box(const f32x4 b, float scale, float flip_w) {
+    const float x1 = __fdiv_rn(b[0], scale), y1 = __fdiv_rn(b[1], scale), x2 = __fdiv_rn(b[2], scale), y2 = __fdiv_rn(b[3], scale);
+    f32x4 o = {x1, y1, x2, y2};
+    if (flip_w > 0.f) {
+        o[0] = __fsub_rn(flip_w, x2);
+        o[2] = __fsub_rn(flip_w, x1);
+    }
+    return o;
+}
+
+// The one body of decode_kernel (VIEW = false) and decode_view_kernel (VIEW = true: section 1b; `scale` and `flip_w` are read only there).  The two entry points declare
+// the record buffers -- (4 waves, DEC_BUF) each, in LDS -- and pass them in.
+template <bool VIEW>
+__device__ __forceinline__ void decode_body(const DecodeArgs& a, float scale, float flip_w, uint64_t* buf_hi, uint32_t* buf_lo) {
     // One wave walks DEC_PIX_PER_WAVE consecutive pixels.  Candidates are appended to a per-wave LDS
     // buffer and flushed with a single atomicAdd on the global counter (one hot word saturates at
     // ~88 atomics/us: one atomic per pixel made this kernel atomic-bound).
-    __shared__ uint64_t buf_hi[4][DEC_BUF];
-    __shared__ uint32_t buf_lo[4][DEC_BUF];
     const CandSink& k_ = a.sink;
     const int lane = threadIdx.x & 63;
     const int wl = threadIdx.x >> 6;
@@ -74,8 +87,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
     const int hw = a.h * a.w;
     const int nch = 3 * a.K;
     const int npass = cdiv(nch, 256);
-    uint64_t* bhi = buf_hi[wl];
-    uint32_t* blo = buf_lo[wl];
+    uint64_t* bhi = buf_hi + wl * DEC_BUF;
+    uint32_t* blo = buf_lo + wl * DEC_BUF;
     int fill = 0;      // records in the LDS buffer (wave-uniform)
     int fill_img = 0;  // image the buffered records belong to (per-image path flushes on image change)
 
@@ -104,7 +117,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
         }
         if (lane < 3) {
             const float* r = row + lane * a.K;
-            const f32x4 b = decode_box(r[0], r[1], r[2], r[3], x, y, a.stride, a.anc[2 * lane], a.anc[2 * lane + 1]);
+            f32x4 b = decode_box(r[0], r[1], r[2], r[3], x, y, a.stride, a.anc[2 * lane], a.anc[2 * lane + 1]);
+            if constexpr (VIEW) b = descale_box(b, scale, flip_w);
             const int anchor = a.level_off + (lane * a.h + y) * a.w + x;
             *reinterpret_cast<f32x4*>(k_.boxes_all + ((int64_t)img * k_.total_anchors + anchor) * 4) = b;
         }
@@ -213,13 +227,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
     flush();
 }
 
+__global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
+    __shared__ uint64_t buf_hi[4][DEC_BUF];
+    __shared__ uint32_t buf_lo[4][DEC_BUF];
+    decode_body<false>(a, 1.f, 0.f, &buf_hi[0][0], &buf_lo[0][0]);
+}
+
 // ------------------------------------------------------------------------------------------
-// 1b. decode + threshold of ONE VIEW of augmented inference (ymi_post_decode_view; ultralytics' _forward_augment, yolort/v5/models/yolo.py:152-163): decode_kernel's twin.
-//     decode_kernel keeps its own text (and with it its instructions: the default path must not move); this kernel restates it with two differences, both in the three
-//     box lanes: the decoded corners are brought back to the full canvas (_descale_pred, yolo.py:181-197 -- y' = y / scale, x' = x / scale, or mirrored
-//     x1' = W - x2 / scale, x2' = W - x1 / scale; every operation an explicitly rounded fp32 one), and `level_off` already holds the view's anchor base plus the kept levels
-//     in front of this one, so records and boxes land in the view's range of the concatenated anchor axis (torch.cat(y, 1) after _clip_augmented).  Scores, thresholds,
-//     best-class mode and the class filter are decode_kernel's statements.
+// 1b. decode + threshold of ONE VIEW of augmented inference (ymi_post_decode_view; ultralytics' _forward_augment, yolort/v5/models/yolo.py:152-163): decode_body<true>.
+//     A view changes two things, both in the three box lanes: the decoded corners are brought back to the full canvas (descale_box), and `level_off` already holds the
+//     view's anchor base plus the kept levels in front of this one, so records and boxes land in the view's range of the concatenated anchor axis (torch.cat(y, 1) after
+//     _clip_augmented).
 // ------------------------------------------------------------------------------------------
 struct DecodeViewArgs {
     DecodeArgs d;
@@ -227,158 +245,10 @@ struct DecodeViewArgs {
     float flip_w;          // > 0: the view was mirrored left-right, the full canvas width W as a float; 0: not mirrored
 };
 
-__device__ __forceinline__ f32x4 descale_box(const f32x4 b, float scale, float flip_w) {
-    const float x1 = __fdiv_rn(b[0], scale), y1 = __fdiv_rn(b[1], scale), x2 = __fdiv_rn(b[2], scale), y2 = __fdiv_rn(b[3], scale);
-    f32x4 o = {x1, y1, x2, y2};
-    if (flip_w > 0.f) {
-        o[0] = __fsub_rn(flip_w, x2);
-        o[2] = __fsub_rn(flip_w, x1);
-    }
-    return o;
-}
-
 __global__ __launch_bounds__(256) void decode_view_kernel(const DecodeViewArgs va) {
     __shared__ uint64_t buf_hi[4][DEC_BUF];
     __shared__ uint32_t buf_lo[4][DEC_BUF];
-    const DecodeArgs& a = va.d;
-    const CandSink& k_ = a.sink;
-    const int lane = threadIdx.x & 63;
-    const int wl = threadIdx.x >> 6;
-    const int64_t wave = (int64_t)blockIdx.x * 4 + wl;
-    const int64_t npix = (int64_t)a.n * a.h * a.w;
-    const int hw = a.h * a.w;
-    const int nch = 3 * a.K;
-    const int npass = cdiv(nch, 256);
-    uint64_t* bhi = buf_hi[wl];
-    uint32_t* blo = buf_lo[wl];
-    int fill = 0;      // records in the LDS buffer (wave-uniform)
-    int fill_img = 0;  // image the buffered records belong to (per-image path flushes on image change)
-
-    auto flush = [&]() {
-        flush_records(k_, bhi, blo, fill, fill_img, lane);
-        __builtin_amdgcn_wave_barrier();   // see decode_kernel
-        fill = 0;
-    };
-
-    for (int pp = 0; pp < DEC_PIX_PER_WAVE; ++pp) {
-        const int64_t pix = wave * DEC_PIX_PER_WAVE + pp;
-        if (pix >= npix) break;
-        const int img = (int)(pix / hw);
-        const int rem = (int)(pix - (int64_t)img * hw);
-        const int y = rem / a.w, x = rem - y * a.w;
-        const float* row = a.logits + pix * a.cs;
-        float obj[3];
-        bool any_obj = false;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            obj[k] = sigmoid_acc(row[k * a.K + 4]);
-            any_obj |= obj[k] > k_.thr;
-        }
-        if (lane < 3) {
-            const float* r = row + lane * a.K;
-            const f32x4 b = descale_box(decode_box(r[0], r[1], r[2], r[3], x, y, a.stride, a.anc[2 * lane], a.anc[2 * lane + 1]), va.scale, va.flip_w);
-            const int anchor = a.level_off + (lane * a.h + y) * a.w + x;
-            *reinterpret_cast<f32x4*>(k_.boxes_all + ((int64_t)img * k_.total_anchors + anchor) * 4) = b;
-        }
-        if (!any_obj) continue;
-        if (fill + (k_.best ? 3 : nch) > DEC_BUF || img != fill_img) flush();
-        fill_img = img;
-        if (k_.best) {
-            BestClass b0 = best_none(), b1 = best_none(), b2 = best_none();
-            for (int p = 0; p < npass; ++p) {
-                const int c0 = (p * 64 + lane) * 4;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (c0 + 3 < nch) v = *reinterpret_cast<const f32x4*>(row + c0);
-                else
-                    for (int e = 0; e < 4; ++e)
-                        if (c0 + e < nch) v[e] = row[c0 + e];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = c0 + e;
-                    const int k = c / a.K, cls = c - k * a.K - 5;
-                    const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
-                    if (c < nch && cls >= 0 && o > k_.thr) {
-                        const float s = __fmul_rn(sigmoid_acc(v[e]), o);
-                        BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
-                        if (best_before(s, cls, b)) b = BestClass{s, cls};
-                    }
-                }
-            }
-            int cnt = 0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (!(obj[k] > k_.thr)) continue;
-                BestClass& b = k == 0 ? b0 : (k == 1 ? b1 : b2);
-#pragma unroll
-                for (int d = 32; d >= 1; d >>= 1) {
-                    const BestClass t = {__shfl_xor(b.s, d, 64), __shfl_xor(b.c, d, 64)};
-                    if (best_before(t.s, t.c, b)) b = t;
-                }
-                if (b.c != 0x7fffffff && b.s > k_.thr && (k_.cmask == nullptr || class_allowed(k_.cmask, b.c))) {
-                    if (lane == 0) {
-                        const int anchor = a.level_off + (k * a.h + y) * a.w + x;
-                        bhi[fill + cnt] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(b.s));
-                        blo[fill + cnt] = ((unsigned)anchor << k_.label_bits) | (unsigned)b.c;
-                    }
-                    ++cnt;
-                }
-            }
-            fill += cnt;
-            continue;
-        }
-        for (int p = 0; p < npass; ++p) {
-            const int c0 = (p * 64 + lane) * 4;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (c0 + 3 < nch) v = *reinterpret_cast<const f32x4*>(row + c0);
-            else
-                for (int e = 0; e < 4; ++e)
-                    if (c0 + e < nch) v[e] = row[c0 + e];
-            float sc[4];
-            unsigned cand[4];
-            int cnt = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int c = c0 + e;
-                const int k = c / a.K, cls = c - k * a.K - 5;
-                bool ok = (c < nch) && (cls >= 0);
-                float s = 0.f;
-                if (ok) {
-                    const float o = k == 0 ? obj[0] : (k == 1 ? obj[1] : obj[2]);
-                    s = __fmul_rn(sigmoid_acc(v[e]), o);
-                    ok = s > k_.thr;
-                    if (k_.cmask != nullptr) ok = ok && class_allowed(k_.cmask, cls);
-                }
-                sc[e] = s;
-                const int anchor = a.level_off + (k * a.h + y) * a.w + x;
-                cand[e] = ((unsigned)anchor << k_.label_bits) | (unsigned)(cls < 0 ? 0 : cls);
-                if (!ok) cand[e] = 0xffffffffu;
-                cnt += ok ? 1 : 0;
-            }
-            int incl = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += t;
-            }
-            const int total = __shfl(incl, 63, 64);
-            if (total == 0) continue;
-            if (fill + total > DEC_BUF) flush();
-            int pos = fill + incl - cnt;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (cand[e] != 0xffffffffu) {
-                    if (pos < DEC_BUF) {
-                        bhi[pos] = ((uint64_t)(unsigned)img << 32) | (uint64_t)(~__float_as_uint(sc[e]));
-                        blo[pos] = cand[e];
-                    }
-                    ++pos;
-                }
-            }
-            fill += total;
-            if (fill > DEC_BUF) fill = DEC_BUF;
-        }
-    }
-    flush();
+    decode_body<true>(va.d, va.scale, va.flip_w, &buf_hi[0][0], &buf_lo[0][0]);
 }
 
 __global__ void finalize_count_kernel(int* status, int cap) {
@@ -1285,6 +1155,43 @@ __device__ __forceinline__ bool iou_gt(const f32x4 bi, float area_i, const f32x4
     return iou > thr;
 }
 
+// ---- the greedy step both NMS kernels (3, 3b) are made of: lane l holds candidate l of the step's 64 ----
+__device__ __forceinline__ float box_area(const f32x4 b) { return __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1])); }
+
+// candidate at position p of the order P: its rank r in G, its box (looked up by image and anchor) and area; zeros for a lane without a candidate
+struct NmsCand { f32x4 box; float area; unsigned r; };
+__device__ __forceinline__ NmsCand nms_load_candidate(bool valid, int p, const uint32_t* plo, const uint64_t* ghi, const uint32_t* glo, const float* boxes_all,
+                                                      int total_anchors, int label_bits) {
+    NmsCand c = {{0.f, 0.f, 0.f, 0.f}, 0.f, 0u};
+    if (valid) {
+        c.r = plo[p];
+        const unsigned img = (unsigned)(ghi[c.r] >> 32);
+        const unsigned anchor = glo[c.r] >> label_bits;
+        c.box = *reinterpret_cast<const f32x4*>(boxes_all + ((int64_t)img * total_anchors + anchor) * 4);
+    }
+    c.area = box_area(c.box);
+    return c;
+}
+
+// against the boxes already kept in the segment (higher score), entries first, first + stride, ...: LDS broadcast reads of `kl` below kcap, the spill area `kb` beyond
+// (kcap is a multiple of stride)
+__device__ __forceinline__ bool nms_test_kept(bool alive, const NmsCand& c, const f32x4* kl, const f32x4* kb, int kept_cnt, int kcap, int first, int stride, float thr) {
+    const int in_lds = kept_cnt < kcap ? kept_cnt : kcap;
+    for (int j = first; j < in_lds; j += stride) {
+        const f32x4 k = kl[j];
+        if (alive && iou_gt(k, box_area(k), c.box, c.area, thr)) alive = false;
+    }
+    for (int j = kcap + first; j < kept_cnt; j += stride) {
+        const f32x4 k = kb[j];
+        if (alive && iou_gt(k, box_area(k), c.box, c.area, thr)) alive = false;
+    }
+    return alive;
+}
+
+// The third piece of the step -- the 64 candidates resolved among themselves by ballot and shuffle, the survivors appended to the kept list -- stays written out in
+// both kernels: as a shared helper it compiled nms_block_kernel to a different register assignment that cost ymi_nms 2 to 4 % at 16384 boxes
+// (profiles/post_refactor_bench_ab.txt); written out, both kernels have the parent's instructions but for the order of a few prologue lines.
+
 constexpr int NMS_KCAP = 384;   // kept boxes per wave held in LDS (6 KiB / wave); the rest spills to HBM scratch
 
 __global__ __launch_bounds__(256) void nms_segments_kernel(const uint64_t* phi, const uint32_t* plo, const uint64_t* ghi, const uint32_t* glo,
@@ -1309,48 +1216,28 @@ __global__ __launch_bounds__(256) void nms_segments_kernel(const uint64_t* phi, 
             const bool valid = p < n && phi[p] == key;
             const uint64_t vmask = __ballot(valid);
             if (vmask == 0) break;
-            f32x4 box = {0.f, 0.f, 0.f, 0.f};
-            unsigned r = 0;
-            if (valid) {
-                r = plo[p];
-                const unsigned img = (unsigned)(ghi[r] >> 32);
-                const unsigned anchor = glo[r] >> label_bits;
-                box = *reinterpret_cast<const f32x4*>(boxes_all + ((int64_t)img * total_anchors + anchor) * 4);
-            }
-            const float area = __fmul_rn(__fsub_rn(box[2], box[0]), __fsub_rn(box[3], box[1]));
-            bool alive = valid;
-            // against boxes already kept in this segment (higher score): LDS broadcast reads, HBM beyond NMS_KCAP
-            const int in_lds = kept_cnt < NMS_KCAP ? kept_cnt : NMS_KCAP;
-            for (int j = 0; j < in_lds; ++j) {
-                const f32x4 k = kl[j];
-                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
-                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
-            }
-            for (int j = NMS_KCAP; j < kept_cnt; ++j) {
-                const f32x4 k = kb[j];
-                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
-                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
-            }
-            // among the 64 candidates of this step, in order
+            const NmsCand cand = nms_load_candidate(valid, p, plo, ghi, glo, boxes_all, total_anchors, label_bits);
+            bool alive = nms_test_kept(valid, cand, kl, kb, kept_cnt, NMS_KCAP, 0, 1, thr);
             uint64_t mask = __ballot(alive);
+            // among the 64 candidates of this step, in order
             uint64_t todo = mask;
             while (todo) {
                 const int i = __ffsll((long long)todo) - 1;
                 todo &= todo - 1;
                 f32x4 bi;
-                bi[0] = __shfl(box[0], i, 64);
-                bi[1] = __shfl(box[1], i, 64);
-                bi[2] = __shfl(box[2], i, 64);
-                bi[3] = __shfl(box[3], i, 64);
-                const float ai = __shfl(area, i, 64);
-                if (alive && lane > i && iou_gt(bi, ai, box, area, thr)) alive = false;
+                bi[0] = __shfl(cand.box[0], i, 64);
+                bi[1] = __shfl(cand.box[1], i, 64);
+                bi[2] = __shfl(cand.box[2], i, 64);
+                bi[3] = __shfl(cand.box[3], i, 64);
+                const float ai = __shfl(cand.area, i, 64);
+                if (alive && lane > i && iou_gt(bi, ai, cand.box, cand.area, thr)) alive = false;
                 mask = __ballot(alive);
                 todo &= mask;
             }
             if (alive) {
                 const int slot = kept_cnt + __popcll(mask & lt);
-                if (slot < NMS_KCAP) kl[slot] = box; else kb[slot] = box;
-                keep[r] = 1;
+                if (slot < NMS_KCAP) kl[slot] = cand.box; else kb[slot] = cand.box;
+                keep[cand.r] = 1;
             }
             kept_cnt += __popcll(mask);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // kept boxes (LDS / HBM) visible to this wave's later reads
@@ -1361,8 +1248,8 @@ __global__ __launch_bounds__(256) void nms_segments_kernel(const uint64_t* phi, 
 
 // ------------------------------------------------------------------------------------------
 // 3b. class-AGNOSTIC NMS (YMI_POST_AGNOSTIC, ymi_nms): one segment per IMAGE, whatever the labels.  nms_segments_kernel would give the whole image to one
-//     wave -- the greedy scan of a crowded image on 1/1024 of the chip -- so here a segment gets a WORKGROUP of NMSB_WAVES waves.  The algorithm is the one
-//     above, step for step, hence bit-identical to it: candidates in score order, 64 per step; every wave holds the step's 64 candidates (lane l = candidate
+//     wave -- the greedy scan of a crowded image on 1/1024 of the chip -- so here a segment gets a WORKGROUP of NMSB_WAVES waves.  The step is the one
+//     above -- the same two helpers and the same resolve loop --, hence bit-identical to it: candidates in score order, 64 per step; every wave holds the step's 64 candidates (lane l = candidate
 //     l) and tests them against ITS share of the kept list (kept boxes j = wave, wave + NMSB_WAVES, ...: LDS broadcast reads, the spill area beyond
 //     NMSB_KCAP); the per-wave alive masks meet in LDS; wave 0 ANDs them, resolves the 64 among themselves by ballot and shuffle, appends the survivors to
 //     the kept list and publishes the step's final mask.  Suppression is an OR over the kept boxes, so splitting the list over waves cannot change a bit.
@@ -1403,55 +1290,35 @@ __global__ __launch_bounds__(NMSB_WAVES * 64) void nms_block_kernel(const uint64
         for (int st = 0; st < nsteps; ++st) {
             const int p = start + st * 64 + lane;
             const bool valid = p < end;
-            f32x4 box = {0.f, 0.f, 0.f, 0.f};
-            unsigned r = 0;
-            if (valid) {
-                r = plo[p];
-                const unsigned img = (unsigned)(ghi[r] >> 32);
-                const unsigned anchor = glo[r] >> label_bits;
-                box = *reinterpret_cast<const f32x4*>(boxes_all + ((int64_t)img * total_anchors + anchor) * 4);
-            }
-            const float area = __fmul_rn(__fsub_rn(box[2], box[0]), __fsub_rn(box[3], box[1]));
-            bool alive = valid;
-            // this wave's share of the boxes already kept (higher score)
-            const int in_lds = kept_cnt < NMSB_KCAP ? kept_cnt : NMSB_KCAP;
-            for (int j = wave; j < in_lds; j += NMSB_WAVES) {
-                const f32x4 k = kept_lds[j];
-                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
-                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
-            }
-            for (int j = NMSB_KCAP + wave; j < kept_cnt; j += NMSB_WAVES) {   // (NMSB_KCAP is a multiple of NMSB_WAVES)
-                const f32x4 k = kb[j];
-                const float ka = __fmul_rn(__fsub_rn(k[2], k[0]), __fsub_rn(k[3], k[1]));
-                if (alive && iou_gt(k, ka, box, area, thr)) alive = false;
-            }
-            const uint64_t mine = __ballot(alive);
+            const NmsCand cand = nms_load_candidate(valid, p, plo, ghi, glo, boxes_all, total_anchors, label_bits);
+            // this wave's share of the boxes already kept
+            const uint64_t mine = __ballot(nms_test_kept(valid, cand, kept_lds, kb, kept_cnt, NMSB_KCAP, wave, NMSB_WAVES, thr));
             if (lane == 0) s_alive[wave] = mine;
             __syncthreads();
             if (wave == 0) {
                 uint64_t mask = s_alive[0];
 #pragma unroll
                 for (int w = 1; w < NMSB_WAVES; ++w) mask &= s_alive[w];
-                alive = (mask >> lane) & 1ull;
+                bool alive = (mask >> lane) & 1ull;
                 // among the 64 candidates of this step, in order
                 uint64_t todo = mask;
                 while (todo) {
                     const int i = __ffsll((long long)todo) - 1;
                     todo &= todo - 1;
                     f32x4 bi;
-                    bi[0] = __shfl(box[0], i, 64);
-                    bi[1] = __shfl(box[1], i, 64);
-                    bi[2] = __shfl(box[2], i, 64);
-                    bi[3] = __shfl(box[3], i, 64);
-                    const float ai = __shfl(area, i, 64);
-                    if (alive && lane > i && iou_gt(bi, ai, box, area, thr)) alive = false;
+                    bi[0] = __shfl(cand.box[0], i, 64);
+                    bi[1] = __shfl(cand.box[1], i, 64);
+                    bi[2] = __shfl(cand.box[2], i, 64);
+                    bi[3] = __shfl(cand.box[3], i, 64);
+                    const float ai = __shfl(cand.area, i, 64);
+                    if (alive && lane > i && iou_gt(bi, ai, cand.box, cand.area, thr)) alive = false;
                     mask = __ballot(alive);
                     todo &= mask;
                 }
                 if (alive) {
                     const int slot = kept_cnt + __popcll(mask & lt);
-                    if (slot < NMSB_KCAP) kept_lds[slot] = box; else kb[slot] = box;
-                    keep[r] = 1;
+                    if (slot < NMSB_KCAP) kept_lds[slot] = cand.box; else kb[slot] = cand.box;
+                    keep[cand.r] = 1;
                 }
                 if (lane == 0) s_final = mask;
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // kept boxes (LDS / HBM) visible to the block's later reads
@@ -1848,76 +1715,82 @@ static bool nms_block_enabled() {
     return on;
 }
 
-// segments -> NMS -> top-k gather, given G (arrays w.hi/lo[g]) and the order P the NMS walks: per (image, class) by default, per image (== G's order, every record keyed
-// with label 0) under YMI_POST_AGNOSTIC, where a segment gets a workgroup (nms_block_kernel) instead of a wave
-static int nms_gather(const Workspace& w, int g, const uint64_t* phi, const uint32_t* plo, int* status, int cap, int n_img, int label_bits, int total_anchors,
-                      float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count, hipStream_t s,
-                      const int* truncated = nullptr, float* out_slab = nullptr, const int* img_count = nullptr, bool agnostic = false, int merge_flags = 0) {
-    const int nthr_blocks = cdiv(cap, 256);
-    uint32_t* seg_start = w.seg_start;
-    float* kept_box = w.kept_box;
-    hipLaunchKernelGGL(find_segments_kernel, dim3(nthr_blocks), dim3(256), 0, s, phi, status, cap, seg_start);
-    if (agnostic && nms_block_enabled())   // at most n_img segments
-        hipLaunchKernelGGL(nms_block_kernel, dim3(n_img), dim3(NMSB_WAVES * 64), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
-                           seg_start, kept_box, w.keep, nms_thresh);
-    else
-        hipLaunchKernelGGL(nms_segments_kernel, dim3(1024), dim3(256), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
-                           seg_start, kept_box, w.keep, nms_thresh);
-    GatherArgs ga;
-    ga.ghi = w.hi[g]; ga.glo = w.lo[g]; ga.keep = w.keep; ga.boxes_all = w.boxes_all; ga.rescale = rescale; ga.status = status;
-    ga.truncated = truncated; ga.status_rw = status; ga.out_slab = out_slab; ga.img_count = img_count;
-    ga.cap = cap; ga.total_anchors = total_anchors; ga.label_bits = label_bits; ga.K = K;
-    ga.out_boxes = out_boxes; ga.out_scores = out_scores; ga.out_labels = out_labels; ga.out_count = out_count;
-    if (merge_flags & YMI_POST_MERGE) {   // merge-NMS: the reduction and the gather in one kernel, launched instead of the plain gather
-        const size_t lds = merge_lds_bytes(K);
-        if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)merge_gather_kernel, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
-        hipLaunchKernelGGL(merge_gather_kernel, dim3(n_img), dim3(MRG_THREADS), lds, s, ga, nms_thresh, agnostic ? 1 : 0, (merge_flags & YMI_POST_MERGE_KEEP_SINGLE) ? 1 : 0,
-                           merge_kept_cap(K));
-        return check_launch("nms/merge_gather");
-    }
-    hipLaunchKernelGGL(gather_topk_kernel, dim3(n_img), dim3(256), 0, s, ga);
-    return check_launch("nms/gather");
+// the radix passes over the key bits [lo, hi), 8 per pass
+static int radix_passes(const Workspace& w, SortState& st, int* status, int cap, int lo, int hi, hipStream_t s) {
+    int rc;
+    for (int sh = lo; sh < hi; sh += 8)
+        if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
+    return YMI_OK;
 }
 
-// sorts records in w.hi/lo[st.cur] by (img, score desc, cand asc), then runs NMS + gather.
-static int sort_nms_gather(const Workspace& w, SortState st, int* status, int cap, int n_img, int lo_bits, int label_bits, int total_anchors,
-                           float nms_thresh, int K, const float* rescale, float* out_boxes, float* out_scores, int64_t* out_labels, int* out_count,
-                           hipStream_t s, float* out_slab = nullptr, bool agnostic = false, int merge_flags = 0) {
-    int rc;
-    for (int sh = 0; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
-    for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
-    const int img_bits = bits_for(n_img);
-    for (int sh = 64; sh < 64 + img_bits; sh += 8) if ((rc = radix_pass(w, st, status, cap, sh, s)) != YMI_OK) return rc;
-    // G = current arrays; P = the other pair, re-keyed by label
-    const int g = st.cur, p = st.cur ^ 1;
-    const int nthr_blocks = cdiv(cap, 256);
-    const int p_bits = agnostic ? 0 : label_bits;   // class-agnostic: every record is keyed with label 0 and no label pass follows -- P is G's order, segments are images
-    hipLaunchKernelGGL(make_label_records_kernel, dim3(nthr_blocks), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, cap, p_bits, w.keep);
-    // The label passes ping-pong between P and a scratch pair; G must stay intact, so P's partner
-    // arrays are carved from seg_start/kept_box which are not live yet.
+// The order P the NMS walks, from G (arrays w.hi/lo[g]): every record re-keyed with the low p_bits of its label (make_label_records_kernel, into the other pair), then
+// stably sorted by that label.  p_bits == 0: every record is keyed with label 0 and no pass follows -- P is G's order, a segment is an image.  The label passes
+// ping-pong between P and a scratch pair carved from kept_box / seg_start, which are not live yet (G must stay intact); a P that ends in the scratch is copied back.
+static int label_order(const Workspace& w, int g, int* status, int cap, int p_bits, hipStream_t s, const uint64_t*& phi, const uint32_t*& plo) {
+    const int p = g ^ 1;
+    hipLaunchKernelGGL(make_label_records_kernel, dim3(cdiv(cap, 256)), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, cap, p_bits, w.keep);
     Workspace wl = w;
     wl.hi[0] = w.hi[p];
     wl.lo[0] = w.lo[p];
     wl.hi[1] = reinterpret_cast<uint64_t*>(w.kept_box);        // cap * 16 bytes >= cap * 8
     wl.lo[1] = w.seg_start;                                   // cap * 4 bytes
     SortState sl{0};
-    int label_passes = 0;
-    for (int sh = 32; sh < 32 + p_bits; sh += 8) {
-        if ((rc = radix_pass(wl, sl, status, cap, sh, s)) != YMI_OK) return rc;
-        ++label_passes;
-    }
-    const uint64_t* phi = wl.hi[sl.cur];
-    const uint32_t* plo = wl.lo[sl.cur];
+    int rc;
+    if ((rc = radix_passes(wl, sl, status, cap, 32, 32 + p_bits, s)) != YMI_OK) return rc;
     if (sl.cur == 1) {
-        // sorted P currently lives in the scratch (kept_box/seg_start): move it back to P's own arrays
         YMI_CHECK_HIP(hipMemcpyAsync(w.hi[p], wl.hi[1], (size_t)cap * 8, hipMemcpyDeviceToDevice, s));
         YMI_CHECK_HIP(hipMemcpyAsync(w.lo[p], wl.lo[1], (size_t)cap * 4, hipMemcpyDeviceToDevice, s));
-        phi = w.hi[p];
-        plo = w.lo[p];
     }
-    (void)label_passes;
-    return nms_gather(w, g, phi, plo, status, cap, n_img, label_bits, total_anchors, nms_thresh, K, rescale, out_boxes, out_scores, out_labels, out_count, s, nullptr, out_slab,
-                      nullptr, agnostic, merge_flags);
+    phi = w.hi[p];
+    plo = w.lo[p];
+    return YMI_OK;
+}
+
+// segments of P, then the greedy NMS over them: a workgroup per segment (nms_block_kernel; `block`: the caller's segments are whole images) or a wave per segment
+static void segments_nms(const Workspace& w, int g, const uint64_t* phi, const uint32_t* plo, int* status, int cap, int total_anchors, int label_bits, float nms_thresh,
+                         bool block, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(find_segments_kernel, dim3(cdiv(cap, 256)), dim3(256), 0, s, phi, status, cap, w.seg_start);
+    if (block)
+        hipLaunchKernelGGL(nms_block_kernel, dim3(grid), dim3(NMSB_WAVES * 64), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
+                           w.seg_start, w.kept_box, w.keep, nms_thresh);
+    else
+        hipLaunchKernelGGL(nms_segments_kernel, dim3(grid), dim3(256), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, total_anchors, label_bits, status, cap,
+                           w.seg_start, w.kept_box, w.keep, nms_thresh);
+}
+
+// segments -> NMS -> top-k gather of a descriptor's batch, given G (arrays w.hi/lo[g]) and the order P the NMS walks: per (image, class) by default, per image under
+// YMI_POST_AGNOSTIC, where a segment gets a workgroup instead of a wave
+static int nms_gather(const ymi_post_desc* d, const PostLayout& L, const Workspace& w, int g, const uint64_t* phi, const uint32_t* plo, hipStream_t s) {
+    const bool agnostic = (d->flags & YMI_POST_AGNOSTIC) != 0;
+    const bool block = agnostic && nms_block_enabled();   // at most n segments
+    segments_nms(w, g, phi, plo, d->status, d->cand_cap, L.total_anchors, L.label_bits, d->nms_thresh, block, block ? d->n : 1024, s);
+    const int K = d->detections_per_img;
+    GatherArgs ga;
+    ga.ghi = w.hi[g]; ga.glo = w.lo[g]; ga.keep = w.keep; ga.boxes_all = w.boxes_all; ga.rescale = d->rescale; ga.status = d->status;
+    ga.truncated = L.per_image ? w.sel_count + d->n : nullptr; ga.status_rw = d->status; ga.out_slab = d->out_slab; ga.img_count = L.per_image ? w.img_count : nullptr;
+    ga.cap = d->cand_cap; ga.total_anchors = L.total_anchors; ga.label_bits = L.label_bits; ga.K = K;
+    ga.out_boxes = d->out_boxes; ga.out_scores = d->out_scores; ga.out_labels = d->out_labels; ga.out_count = d->out_count;
+    if (d->flags & YMI_POST_MERGE) {   // merge-NMS: the reduction and the gather in one kernel, launched instead of the plain gather
+        const size_t lds = merge_lds_bytes(K);
+        if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)merge_gather_kernel, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
+        hipLaunchKernelGGL(merge_gather_kernel, dim3(d->n), dim3(MRG_THREADS), lds, s, ga, d->nms_thresh, agnostic ? 1 : 0, (d->flags & YMI_POST_MERGE_KEEP_SINGLE) ? 1 : 0,
+                           merge_kept_cap(K));
+        return check_launch("nms/merge_gather");
+    }
+    hipLaunchKernelGGL(gather_topk_kernel, dim3(d->n), dim3(256), 0, s, ga);
+    return check_launch("nms/gather");
+}
+
+// the global-sort path: sorts the records in w.hi/lo[0] by (img, score desc, cand asc), then runs NMS + gather
+static int sort_nms_gather(const ymi_post_desc* d, const PostLayout& L, const Workspace& w, hipStream_t s) {
+    int rc;
+    SortState st{0};
+    if ((rc = radix_passes(w, st, d->status, d->cand_cap, 0, L.label_bits + L.anchor_bits, s)) != YMI_OK) return rc;
+    if ((rc = radix_passes(w, st, d->status, d->cand_cap, 32, 64 + bits_for(d->n), s)) != YMI_OK) return rc;   // score, then image
+    const uint64_t* phi;
+    const uint32_t* plo;
+    if ((rc = label_order(w, st.cur, d->status, d->cand_cap, (d->flags & YMI_POST_AGNOSTIC) ? 0 : L.label_bits, s, phi, plo)) != YMI_OK) return rc;
+    return nms_gather(d, L, w, st.cur, phi, plo, s);
 }
 
 // The batch size a descriptor may carry: the per-image path ranks the whole batch through one LDS table (rank_image_kernel), and include/yolort_amd.h gives that limit
@@ -2000,6 +1873,23 @@ int post_set_classes_launch(const ymi_post_desc* d, const int32_t* classes, int 
     return check_launch("class_mask_write_kernel");
 }
 
+// DecodeArgs of level l of `src` feeding the sink of `d`.  `src` is the descriptor itself or a view (ymi_post_view): the two structs give a level's fields the same names
+// (logits, lh, lw, lcstride, stride, anchors), which is all this template relies on.
+template <class Levels>
+static DecodeArgs level_args(const ymi_post_desc* d, const Workspace& w, const PostLayout& L, const Levels* src, int l, int level_off) {
+    DecodeArgs a;
+    a.logits = src->logits[l]; a.h = src->lh[l]; a.w = src->lw[l]; a.cs = src->lcstride[l]; a.stride = src->stride[l];
+    for (int k = 0; k < 6; ++k) a.anc[k] = src->anchors[l][k];
+    a.n = d->n; a.K = d->num_classes + 5; a.level_off = level_off;
+    a.sink = make_sink(d, w, L);
+    return a;
+}
+// blocks of four waves that walk DEC_PIX_PER_WAVE pixels each
+static dim3 decode_grid(const DecodeArgs& a) {
+    const int64_t npix = (int64_t)a.n * a.h * a.w;
+    return dim3((unsigned)((npix + 4 * DEC_PIX_PER_WAVE - 1) / (4 * DEC_PIX_PER_WAVE)));
+}
+
 // stage 2 of 3 (unfused form): decode + threshold of the fp32 head outputs
 static int post_decode_launch(const ymi_post_desc* d, hipStream_t s) {
     PostLayout L;
@@ -2008,13 +1898,8 @@ static int post_decode_launch(const ymi_post_desc* d, hipStream_t s) {
     if (rc != YMI_OK) return rc;
     int level_off = 0;
     for (int l = 0; l < d->num_levels; ++l) {
-        DecodeArgs a;
-        a.logits = d->logits[l]; a.h = d->lh[l]; a.w = d->lw[l]; a.cs = d->lcstride[l]; a.stride = d->stride[l];
-        for (int k = 0; k < 6; ++k) a.anc[k] = d->anchors[l][k];
-        a.n = d->n; a.K = d->num_classes + 5; a.level_off = level_off;
-        a.sink = make_sink(d, w, L);
-        const int64_t npix = (int64_t)d->n * a.h * a.w;
-        hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((npix + 4 * DEC_PIX_PER_WAVE - 1) / (4 * DEC_PIX_PER_WAVE))), dim3(256), 0, s, a);
+        const DecodeArgs a = level_args(d, w, L, d, l, level_off);
+        hipLaunchKernelGGL(decode_kernel, decode_grid(a), dim3(256), 0, s, a);
         level_off += 3 * a.h * a.w;
     }
     return check_launch("decode_kernel");
@@ -2044,16 +1929,9 @@ int post_decode_view_launch(const ymi_post_desc* d, const ymi_post_view* v, hipS
     int level_off = v->anchor_base;
     for (int l = 0; l < v->num_levels; ++l) {
         if ((v->skip_mask >> l) & 1) continue;   // a clipped tail: no launch, no anchor indices
-        DecodeViewArgs va;
-        DecodeArgs& a = va.d;
-        a.logits = v->logits[l]; a.h = v->lh[l]; a.w = v->lw[l]; a.cs = v->lcstride[l]; a.stride = v->stride[l];
-        for (int k = 0; k < 6; ++k) a.anc[k] = v->anchors[l][k];
-        a.n = d->n; a.K = d->num_classes + 5; a.level_off = level_off;
-        a.sink = make_sink(d, w, L);
-        va.scale = v->scale; va.flip_w = (float)v->flip_w;
-        const int64_t npix = (int64_t)d->n * a.h * a.w;
-        hipLaunchKernelGGL(decode_view_kernel, dim3((unsigned)((npix + 4 * DEC_PIX_PER_WAVE - 1) / (4 * DEC_PIX_PER_WAVE))), dim3(256), 0, s, va);
-        level_off += 3 * a.h * a.w;
+        const DecodeViewArgs va = {level_args(d, w, L, v, l, level_off), v->scale, (float)v->flip_w};
+        hipLaunchKernelGGL(decode_view_kernel, decode_grid(va.d), dim3(256), 0, s, va);
+        level_off += 3 * va.d.h * va.d.w;
     }
     return check_launch("decode_view_kernel");
 }
@@ -2064,10 +1942,8 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
     Workspace w;
     int rc = post_validate(d, false, L, w);
     if (rc != YMI_OK) return rc;
-    const bool agnostic = (d->flags & YMI_POST_AGNOSTIC) != 0;
-    const int p_bits = agnostic ? 0 : L.label_bits;   // label bits of the P keys: none under YMI_POST_AGNOSTIC (P is G's order, one segment per image)
-    const int merge_flags = d->flags & (YMI_POST_MERGE | YMI_POST_MERGE_KEEP_SINGLE);   // merge-NMS: merge_gather_kernel instead of gather_topk_kernel
     if (L.per_image) {
+        const int p_bits = (d->flags & YMI_POST_AGNOSTIC) ? 0 : L.label_bits;   // label bits of the P keys: none under YMI_POST_AGNOSTIC (P is G's order, one segment per image)
         const int cap_img = L.cap_img;
         const bool exact_full = (d->flags & YMI_POST_EXACT_FULL) != 0;
         const int sel_t = exact_full ? 0 : (4 * d->detections_per_img > 4096 ? 4 * d->detections_per_img : 4096);
@@ -2115,14 +1991,12 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
             hipLaunchKernelGGL(sort_image_kernel, dim3(d->n), dim3(1024), lds, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, d->n, p_bits, lds_keys,
                                RANK_MAX, w.hi[1], w.lo[1], w.p_hi, w.p_lo, w.keep, d->status);
         if ((rc = check_launch("select_prefix/sort_image")) != YMI_OK) return rc;
-        return nms_gather(w, 1, w.p_hi, w.p_lo, d->status, d->cand_cap, d->n, L.label_bits, L.total_anchors, d->nms_thresh, d->detections_per_img, d->rescale,
-                          d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, w.sel_count + d->n, d->out_slab, w.img_count, agnostic, merge_flags);
+        return nms_gather(d, L, w, 1, w.p_hi, w.p_lo, s);
     }
     hipLaunchKernelGGL(finalize_count_kernel, dim3(1), dim3(64), 0, s, d->status, d->cand_cap);
     rc = check_launch("finalize_count");
     if (rc != YMI_OK) return rc;
-    return sort_nms_gather(w, SortState{0}, d->status, d->cand_cap, d->n, L.label_bits + L.anchor_bits, L.label_bits, L.total_anchors, d->nms_thresh,
-                           d->detections_per_img, d->rescale, d->out_boxes, d->out_scores, d->out_labels, d->out_count, s, d->out_slab, agnostic, merge_flags);
+    return sort_nms_gather(d, L, w, s);
 }
 
 int postprocess_launch(const ymi_post_desc* d, hipStream_t s) {
@@ -2203,76 +2077,42 @@ extern "C" int64_t ymi_nms_ws_bytes(int n) {
     return carve(nullptr, 1, n, n).total + 256 /* status */ + 2 * 256;
 }
 
-extern "C" int ymi_batched_nms(const float* boxes, const float* scores, const int32_t* labels, int n, float nms_thresh, int32_t* keep_out,
-                               int32_t* count_out, void* ws, int64_t ws_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    YMI_REQUIRE(count_out && ws, "ymi_batched_nms: null buffer");
+// the two stand-alone entry points: records from the caller's arrays, sort by (score desc, index asc), P keyed by label, segments + NMS, ordered emit of the kept indices.
+// labels == NULL is ymi_nms (torchvision.ops.nms): every record is keyed with label 0 -- nothing to sort below the index, no label passes, ONE segment -- and the
+// segment gets a workgroup (nms_block_kernel) unless YOLORT_AMD_NMS_BLOCK=0
+static int nms_standalone(const char* what, const float* boxes, const float* scores, const int32_t* labels, bool need_labels, int n, float nms_thresh, int32_t* keep_out,
+                          int32_t* count_out, void* ws, int64_t ws_bytes, hipStream_t s) {
+    YMI_REQUIRE(count_out && ws, "%s: null buffer", what);
     if (n == 0) {
         YMI_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int), s));
         return YMI_OK;
     }
-    YMI_REQUIRE(boxes && scores && labels && keep_out, "ymi_batched_nms: null buffer");
-    YMI_REQUIRE(n > 0 && n < (1 << (32 - NMS_LABEL_BITS)), "ymi_batched_nms: n=%d out of range (max %d)", n, (1 << (32 - NMS_LABEL_BITS)) - 1);
-    YMI_REQUIRE(ws_bytes >= ymi_nms_ws_bytes(n), "ymi_batched_nms: workspace too small");
+    YMI_REQUIRE(boxes && scores && (labels || !need_labels) && keep_out, "%s: null buffer", what);
+    YMI_REQUIRE(n > 0 && n < (1 << (32 - NMS_LABEL_BITS)), "%s: n=%d out of range (max %d)", what, n, (1 << (32 - NMS_LABEL_BITS)) - 1);
+    YMI_REQUIRE(ws_bytes >= ymi_nms_ws_bytes(n), "%s: workspace too small", what);
     int* status = (int*)ws;
     const Workspace w = carve((char*)ws + 256, 1, n, n);
     hipLaunchKernelGGL(nms_make_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, boxes, scores, labels, n, w.boxes_all, w.hi[0], w.lo[0], status);
-    // dummy slab outputs for the shared pipeline: carve them after the workspace proper is not possible
-    // without more memory, so the stand-alone path skips gather and emits kept indices itself.
+    // (no slab outputs: the stand-alone path skips the gather and emits the kept indices itself)
+    const int p_bits = labels ? NMS_LABEL_BITS : 0;
     int rc;
     SortState st{0};
-    const int lo_bits = NMS_LABEL_BITS + bits_for(n);
-    for (int sh = 0; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;
-    for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;
-    const int g = st.cur, p = st.cur ^ 1;
-    hipLaunchKernelGGL(make_label_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, n, NMS_LABEL_BITS, w.keep);
-    Workspace wl = w;
-    wl.hi[0] = w.hi[p]; wl.lo[0] = w.lo[p];
-    wl.hi[1] = reinterpret_cast<uint64_t*>(w.kept_box); wl.lo[1] = w.seg_start;
-    SortState sl{0};
-    for (int sh = 32; sh < 32 + NMS_LABEL_BITS; sh += 8) if ((rc = radix_pass(wl, sl, status, n, sh, s)) != YMI_OK) return rc;
-    const uint64_t* phi = wl.hi[sl.cur];
-    const uint32_t* plo = wl.lo[sl.cur];
-    if (sl.cur == 1) {
-        YMI_CHECK_HIP(hipMemcpyAsync(w.hi[p], wl.hi[1], (size_t)n * 8, hipMemcpyDeviceToDevice, s));
-        YMI_CHECK_HIP(hipMemcpyAsync(w.lo[p], wl.lo[1], (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        phi = w.hi[p]; plo = w.lo[p];
-    }
-    hipLaunchKernelGGL(find_segments_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, phi, status, n, w.seg_start);
-    hipLaunchKernelGGL(nms_segments_kernel, dim3(256), dim3(256), 0, s, phi, plo, w.hi[g], w.lo[g], w.boxes_all, n, NMS_LABEL_BITS, status, n, w.seg_start,
-                       w.kept_box, w.keep, nms_thresh);
-    hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(1), dim3(256), 0, s, w.lo[g], w.keep, n, keep_out, count_out);
-    return check_launch("ymi_batched_nms");
+    if ((rc = radix_passes(w, st, status, n, NMS_LABEL_BITS - p_bits, NMS_LABEL_BITS + bits_for(n), s)) != YMI_OK) return rc;
+    if ((rc = radix_passes(w, st, status, n, 32, 64, s)) != YMI_OK) return rc;
+    const uint64_t* phi;
+    const uint32_t* plo;
+    if ((rc = label_order(w, st.cur, status, n, p_bits, s, phi, plo)) != YMI_OK) return rc;
+    const bool block = labels == nullptr && nms_block_enabled();
+    segments_nms(w, st.cur, phi, plo, status, n, n, NMS_LABEL_BITS, nms_thresh, block, labels ? 256 : 1, s);
+    hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(1), dim3(256), 0, s, w.lo[st.cur], w.keep, n, keep_out, count_out);
+    return check_launch(what);
 }
 
-// torchvision.ops.nms: ymi_batched_nms's sequence with every record keyed with label 0 -- no label passes, ONE segment -- and the workgroup-per-segment kernel
+extern "C" int ymi_batched_nms(const float* boxes, const float* scores, const int32_t* labels, int n, float nms_thresh, int32_t* keep_out,
+                               int32_t* count_out, void* ws, int64_t ws_bytes, void* stream) {
+    return nms_standalone("ymi_batched_nms", boxes, scores, labels, true, n, nms_thresh, keep_out, count_out, ws, ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" int ymi_nms(const float* boxes, const float* scores, int n, float nms_thresh, int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    YMI_REQUIRE(count_out && ws, "ymi_nms: null buffer");
-    if (n == 0) {
-        YMI_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int), s));
-        return YMI_OK;
-    }
-    YMI_REQUIRE(boxes && scores && keep_out, "ymi_nms: null buffer");
-    YMI_REQUIRE(n > 0 && n < (1 << (32 - NMS_LABEL_BITS)), "ymi_nms: n=%d out of range (max %d)", n, (1 << (32 - NMS_LABEL_BITS)) - 1);
-    YMI_REQUIRE(ws_bytes >= ymi_nms_ws_bytes(n), "ymi_nms: workspace too small");
-    int* status = (int*)ws;
-    const Workspace w = carve((char*)ws + 256, 1, n, n);
-    hipLaunchKernelGGL(nms_make_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, boxes, scores, (const int*)nullptr, n, w.boxes_all, w.hi[0], w.lo[0], status);
-    int rc;
-    SortState st{0};
-    const int lo_bits = NMS_LABEL_BITS + bits_for(n);
-    for (int sh = NMS_LABEL_BITS; sh < lo_bits; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;   // (the label field is zero: nothing to sort below it)
-    for (int sh = 32; sh < 64; sh += 8) if ((rc = radix_pass(w, st, status, n, sh, s)) != YMI_OK) return rc;
-    const int g = st.cur, p = st.cur ^ 1;
-    hipLaunchKernelGGL(make_label_records_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w.hi[g], w.lo[g], w.hi[p], w.lo[p], status, n, 0, w.keep);   // P = G's order, one key
-    hipLaunchKernelGGL(find_segments_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, w.hi[p], status, n, w.seg_start);
-    if (nms_block_enabled())
-        hipLaunchKernelGGL(nms_block_kernel, dim3(1), dim3(NMSB_WAVES * 64), 0, s, w.hi[p], w.lo[p], w.hi[g], w.lo[g], w.boxes_all, n, NMS_LABEL_BITS, status, n, w.seg_start,
-                           w.kept_box, w.keep, nms_thresh);
-    else
-        hipLaunchKernelGGL(nms_segments_kernel, dim3(1), dim3(256), 0, s, w.hi[p], w.lo[p], w.hi[g], w.lo[g], w.boxes_all, n, NMS_LABEL_BITS, status, n, w.seg_start,
-                           w.kept_box, w.keep, nms_thresh);
-    hipLaunchKernelGGL(nms_emit_keep_kernel, dim3(1), dim3(256), 0, s, w.lo[g], w.keep, n, keep_out, count_out);
-    return check_launch("ymi_nms");
+    return nms_standalone("ymi_nms", boxes, scores, nullptr, false, n, nms_thresh, keep_out, count_out, ws, ws_bytes, (hipStream_t)stream);
 }
