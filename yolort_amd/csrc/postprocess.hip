@@ -530,7 +530,7 @@ __device__ __forceinline__ void hist_add(int* hist, int bin, bool valid) {
 //   sel_compact_kernel   (slices x images)  records of bins <= b* appended to the image's staging region (arrays [1], free until scatter_ranks)
 //                                           at positions handed out by one atomic per wave -- their order does not matter: every consumer ranks
 //                                           by the records' unique keys
-//   sel_copyback_kernel                     staging -> the front of the image's own region (<= RANK_MAX records)
+//   sel_copyback_kernel                     staging -> the front of the image's own region (<= max(RANK_MAX, sel_t) records: blocks stride over the selection)
 // An in-place multi-block compaction would overwrite records of slice 0 that its block may not have read yet.
 // A fat boundary bin (saturated scores: the benchmark configurations' synthetic weights put most images there) is refined by the same exact radix selection as
 // in the one-block kernel, as a fixed LADDER of six (sel_rhist_kernel, sel_rpick_kernel) pairs -- 11 key bits per level; the launch sequence does not depend on the
@@ -720,8 +720,10 @@ __global__ __launch_bounds__(256) void sel_copyback_kernel(uint64_t* hi0, uint32
     const int img = blockIdx.y;
     const int mode = sel_state[SEL_STATE * img];
     if (mode != 1 && mode != 3) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < sel_count[img]) {
+    // EVERY selected record: a refined selection holds up to RANK_MAX records, but with sel_t > RANK_MAX (detections_per_img > 1536) the ladder ends at the exhausted
+    // key with exactly sel_t.  sel_count <= the image's record count <= cap_img.
+    const int n_sel = sel_count[img];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n_sel; i += gridDim.x * 256) {
         hi0[(int64_t)img * cap_img + i] = st_hi[(int64_t)img * cap_img + i];
         lo0[(int64_t)img * cap_img + i] = st_lo[(int64_t)img * cap_img + i];
     }
@@ -737,6 +739,7 @@ __global__ __launch_bounds__(1024) void select_prefix_kernel(uint64_t* in_hi, ui
     const int raw = img_count[img];
     const int n_i = raw < cap_img ? raw : cap_img;
     if (rank_g != nullptr) {   // rank counters of the multi-block ranking sort (rank_image_kernel adds into them)
+        // the first RANK_MAX only: an image that keeps more records (sel_t > RANK_MAX, or YMI_POST_EXACT_FULL) is sort_image_kernel's and never touches the counters
         const int nz = n_i < RANK_MAX ? n_i : RANK_MAX;
         for (int i = threadIdx.x; i < nz; i += blockDim.x) { rank_g[(int64_t)img * cap_img + i] = 0u; rank_p[(int64_t)img * cap_img + i] = 0u; }
     }
@@ -792,10 +795,12 @@ __global__ __launch_bounds__(1024) void select_prefix_kernel(uint64_t* in_hi, ui
     }
     __syncthreads();
     const int bstar = s_bstar, nsel = s_nsel;
-    if (nsel >= n_i) {   // the best bins hold everything: nothing to cut
+    if (nsel >= n_i && nsel <= RANK_MAX) {   // the best bins hold everything and the ranking sort takes it: nothing to cut
         if (threadIdx.x == 0) { sel_count[img] = n_i; sel_count[n_img + img] = 0; }
         return;
     }
+    // (nsel >= n_i > RANK_MAX: the crossing bin is the image's LAST populated bin and fat -- every score equal, or the tail of the image within 1 / 4096 of the
+    // threshold.  It is refined like any other fat bin; leaving the image whole sent all of it to the one-block sort the refinement exists to avoid.)
     if (sel_mode != nullptr) {   // multi-block form: publish the cut (plain), or hand the fat boundary bin to the refinement ladder; sel_compact_kernel moves the records
         if (threadIdx.x == 0) {
             int* st = sel_mode + SEL_STATE * img;
@@ -1975,7 +1980,7 @@ int post_finish_launch(const ymi_post_desc* d, hipStream_t s) {
             hipLaunchKernelGGL(sel_compact_kernel, dim3(nslices, d->n), dim3(1024), 0, s, w.hi[0], w.lo[0], w.img_count, cap_img, sel_state, gfill, w.hi[1], w.lo[1]);
             hipLaunchKernelGGL(sel_copyback_kernel, dim3(cdiv(RANK_MAX, 256), d->n), dim3(256), 0, s, w.hi[0], w.lo[0], w.hi[1], w.lo[1], sel_state, w.sel_count, cap_img);
         }
-        const int rank_cap = cap_img < RANK_MAX ? cap_img : RANK_MAX;   // no image holds more than cap_img records
+        const int rank_cap = cap_img < RANK_MAX ? cap_img : RANK_MAX;   // no image holds more than cap_img records; one that keeps more than RANK_MAX is sort_image_kernel's
         hipLaunchKernelGGL(rank_image_kernel, dim3(RANK_GRID), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.sel_count, d->n, cap_img,
                            p_bits, rank_g, rank_p);
         hipLaunchKernelGGL(scatter_ranks_kernel, dim3(cdiv(rank_cap, RANK_IT), d->n), dim3(RANK_IT), 0, s, w.hi[0], w.lo[0], w.img_count, w.sel_count, cap_img, p_bits,
