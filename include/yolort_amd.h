@@ -476,6 +476,62 @@ int ymi_batched_nms(const float* boxes, const float* scores, const int32_t* labe
 int ymi_nms(const float* boxes, const float* scores, int n, float nms_thresh, int32_t* keep_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * COCO matching on the device: the greedy detection <-> ground-truth matching of the COCO detection protocol (pycocotools COCOeval.evaluateImg, restated on the host by
+ * yolort_amd/utils/metrics.py coco_ap) for the detection slab, one launch for every (image, class, area range, IoU threshold).  Only the matching runs here: the
+ * caller sorts the flags by score and accumulates precision / recall on the host (metrics.py GpuDetectionEvaluator).
+ * Inputs (device, read-only): the slab boxes (n, k, 4) fp32 xyxy, scores (n, k) fp32, labels (n, k) int64, counts (n) int32 -- what the top-k kernel writes and the
+ * ranks all-gather --; ground truth gt_boxes (n, g, 4) fp32 xyxy, gt_labels (n, g) int32, gt_counts (n) int32 (negative counts as 0).  Slots at or past a count are
+ * never read; a counts[i] above k or a gt_counts[i] above g is taken as k / g (the slab holds no more) without a status bit.  Scores may be ANY fp32 values: negative,
+ * +-0 (a tie), +-inf, subnormal, and NaN, which sorts behind every number, in slab order among NaNs -- the total order of the host's stable argsort of -score.  Box
+ * coordinates must not be NaN: a NaN IoU never matches here, while the host loop's `iou < best` is false for it and takes the ground truth.  In the descriptor itself: thrs[num_thrs <= YMI_EVAL_MAX_THRS] IoU thresholds, each in (0, 1]; area_rng[num_rngs <= YMI_EVAL_MAX_RNGS] = {lo, hi};
+ * max_dets (0: no cut); num_classes (<= 4096).  k, g <= YMI_EVAL_MAX_PER_IMAGE; anything larger is refused with YMI_EINVAL, not truncated.
+ * Per (image, class, range r, threshold t):
+ *   - the detections of the class are ordered by score descending, equal scores (-0.0 == +0.0) in slab order, NaN last (a stable sort; the slab need not be sorted); only the
+ *     first max_dets of each (image, class) take part (COCO's maxDets, per category as pycocotools applies it);
+ *   - a ground truth is IGNORED in range r when its area (x2 - x1) * (y2 - y1) (fp32) is < lo or > hi; ground truths are walked non-ignored first, each group in input
+ *     order ({-inf, +inf} ignores nothing: the evaluator's "all" range);
+ *   - IoU = inter / (((area_d + area_g) - inter) + 1e-12f), inter = max(x2 - x1, 0) * max(y2 - y1, 0) of the intersection, every operation a rounded fp32 one and the
+ *     division correctly rounded (zero-area pairs give 0, inverted boxes a negative IoU that never matches);
+ *   - each detection, in score order, takes the still unused ground truth of the largest IoU among those with (double)IoU >= min(t, 1 - 1e-10); among equal IoUs the
+ *     one walked LAST wins; ignored ground truth is looked at only if no non-ignored one qualified;
+ *   - tp = matched a non-ignored ground truth; ig = matched an ignored one or, unmatched, the detection's own area is outside the range.
+ * Outputs (device): tp, ig (num_rngs, n, k) uint16 with bit t per threshold, written for EVERY slot below the image's count (0 for a slot that takes no part) and for
+ * no other; rank (n, k) int32 = the detection's position in its (image, class) score order, -1 when cut by max_dets or skipped, slots at or past the count untouched;
+ * n_gt (num_rngs, num_classes) int32 = non-ignored ground truths per class ADDED to what the buffer holds (integer atomics: the caller zeroes it once and
+ * accumulates over launches), images without detections included; status int32[4], of which the kernel only ever ORs bits into status[1] (the caller zeroes it):
+ * YMI_EVAL_STATUS_BAD_LABEL when a label below a count is outside [0, num_classes) -- that detection (rank -1, flags 0) or ground truth is skipped --,
+ * YMI_EVAL_STATUS_STALE_ROW when a counts[i] is negative (a stale slab row, YMI_SLAB_STALE) -- that image is skipped altogether, its ground truth included.
+ * One workgroup per (image, range) (eval_match_kernel, csrc/postprocess.hip); no workspace; the launch is ordered on `stream`, synchronises nothing and may be captured.
+ * Differences from pycocotools (those of metrics.py): no crowd (iscrowd) ground truth, the 1e-12 in the IoU denominator, areas from the boxes.  ABI stays 6: a new
+ * struct and a new function. */
+#define YMI_EVAL_MAX_THRS 16
+#define YMI_EVAL_MAX_RNGS 4
+#define YMI_EVAL_MAX_PER_IMAGE 1024
+#define YMI_EVAL_STATUS_BAD_LABEL 1 /* status[1] bit 0 */
+#define YMI_EVAL_STATUS_STALE_ROW 2 /* status[1] bit 1 */
+typedef struct ymi_eval_desc {
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const float* gt_boxes;
+    const int32_t* gt_labels;
+    const int32_t* gt_counts;
+    uint16_t* tp;
+    uint16_t* ig;
+    int32_t* rank;
+    int32_t* n_gt;
+    int32_t* status;
+    double thrs[YMI_EVAL_MAX_THRS];
+    float area_rng[YMI_EVAL_MAX_RNGS][2];
+    int32_t n, k, g;
+    int32_t num_thrs, num_rngs;
+    int32_t max_dets, num_classes;
+    int32_t reserved;
+} ymi_eval_desc;
+int ymi_eval_match(const ymi_eval_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Plan: a recorded sequence of the launches above for one (arch, N, H, W, dtype), replayed with a
  * single call (and optionally captured into a hipGraph).  Replaces the Python module-by-module
  * dispatch of yolort/models/yolo.py:159-175.  The plan copies descriptors; buffers stay owned by

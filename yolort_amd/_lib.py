@@ -106,6 +106,22 @@ class PostView(C.Structure):
     ]
 
 
+EVAL_MAX_THRS, EVAL_MAX_RNGS, EVAL_MAX_PER_IMAGE = 16, 4, 1024   # YMI_EVAL_MAX_*
+EVAL_STATUS_BAD_LABEL, EVAL_STATUS_STALE_ROW = 1, 2                # YMI_EVAL_STATUS_*: bits of status[1]
+
+
+class EvalDesc(C.Structure):
+    """ymi_eval_desc: the detection slab, the padded ground truth, the outputs and the protocol (thresholds, area ranges, max_dets) of one ymi_eval_match launch"""
+    _fields_ = [
+        ("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p),
+        ("gt_boxes", C.c_void_p), ("gt_labels", C.c_void_p), ("gt_counts", C.c_void_p),
+        ("tp", C.c_void_p), ("ig", C.c_void_p), ("rank", C.c_void_p), ("n_gt", C.c_void_p), ("status", C.c_void_p),
+        ("thrs", C.c_double * EVAL_MAX_THRS), ("area_rng", (C.c_float * 2) * EVAL_MAX_RNGS),
+        ("n", C.c_int32), ("k", C.c_int32), ("g", C.c_int32), ("num_thrs", C.c_int32), ("num_rngs", C.c_int32),
+        ("max_dets", C.c_int32), ("num_classes", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 VIEW_PAD = 0.447   # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
 TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
 
@@ -177,6 +193,7 @@ _SIGS = {
     "ymi_nms_ws_bytes": (C.c_int64, [C.c_int]),
     "ymi_batched_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ymi_eval_match": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

@@ -2057,6 +2057,275 @@ __global__ __launch_bounds__(256) void nms_emit_keep_kernel(const uint32_t* glo,
     if (threadIdx.x == 0) *count_out = s_base;
 }
 
+// ------------------------------------------------------------------------------------------
+// 7. COCO matching (ymi_eval_match, include/yolort_amd.h): the greedy detection <-> ground-truth matching of yolort_amd/utils/metrics.py coco_ap for the slab, every
+//    (class, threshold) of one (image, area range) in one workgroup.  The image's detections and ground truths are staged in LDS; a detection's rank within its
+//    (image, class) score order is a count over the staged detections; the waves take the classes present in the image in turn (the n-th rank-0 detection of the
+//    slab names the n-th class).  Per class a wave lists its detections in rank order and its ground truths in walk order (non-ignored first), then walks the
+//    detections: lanes run over walk positions strided by 64 and keep, per threshold, the largest key (non-ignored << 63 | IoU bits << 16 | walk position) among
+//    the unused ground truths that qualify -- a qualifying IoU is a positive float, whose bits order as the floats do; the larger position breaks a tie as the
+//    host's `not <` does --, a wave arg-max picks the winner, and the lane that owns the winner's position sets bit t of its 16-bit `used` word.
+//    (double)IoU >= t' is evaluated as IoU >= thr with thr the smallest fp32 not below t' (the launcher computes it): the same predicate on fp32 IoUs.
+// ------------------------------------------------------------------------------------------
+constexpr int EVM_WAVES = 16;     // a power of two: classes are dealt to the waves round-robin (an image of the C2 workload holds ~60 classes)
+constexpr int EVM_IGN = 0x4000;   // a staged ground-truth label carries its ignore flag here (num_classes <= 4096)
+
+struct EvalArgs {
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int* counts;
+    const float* gt_boxes;
+    const int* gt_labels;
+    const int* gt_counts;
+    uint16_t* tp;
+    uint16_t* ig;
+    int* rank;
+    int* n_gt;
+    int* status;
+    int N, K, G, T, R, C, max_dets;
+    float thr[YMI_EVAL_MAX_THRS];
+    float lo[YMI_EVAL_MAX_RNGS], hi[YMI_EVAL_MAX_RNGS];
+};
+
+// byte offsets of the kernel's LDS arrays for slabs of K detections and G ground truths per image
+struct EvalLds {
+    int db, gb, ds, dl, dr, gl, wave0, wave_bytes, ord, walk, used, total;
+};
+__host__ __device__ inline EvalLds eval_lds(int K, int G) {
+    EvalLds L;
+    auto up = [](int v) { return (v + 15) & ~15; };
+    int off = 0;
+    L.db = off; off += K * 16;          // f32x4[K] detection boxes
+    L.gb = off; off += G * 16;          // f32x4[G] ground-truth boxes
+    L.ds = off; off += up(K * 4);       // float[K] scores
+    L.dl = off; off += up(K * 2);       // int16[K] labels, -1 = skipped
+    L.dr = off; off += up(K * 2);       // int16[K] ranks, -1 = takes no part
+    L.gl = off; off += up(G * 2);       // int16[G] labels | EVM_IGN, -1 = skipped
+    L.wave0 = off;
+    L.ord = 0;                          // per wave: uint16[K] slab slot of the class's rank-th detection
+    L.walk = up(K * 2);                 //           uint16[G] ground-truth slot at each walk position
+    L.used = L.walk + up(G * 2);        //           uint16[G] bit t = taken at threshold t, by walk position
+    L.wave_bytes = L.used + up(G * 2);
+    L.total = off + EVM_WAVES * L.wave_bytes;
+    return L;
+}
+
+__device__ __forceinline__ float eval_area(const f32x4 b) { return __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1])); }
+
+// metrics.py _iou_matrix in its order: inter / (((aa + ab) - inter) + 1e-12f)
+__device__ __forceinline__ float eval_iou(const f32x4 a, float aa, const f32x4 b) {
+    const float x1 = a[0] > b[0] ? a[0] : b[0], y1 = a[1] > b[1] ? a[1] : b[1];
+    const float x2 = a[2] < b[2] ? a[2] : b[2], y2 = a[3] < b[3] ? a[3] : b[3];
+    float iw = __fsub_rn(x2, x1), ih = __fsub_rn(y2, y1);
+    iw = iw > 0.f ? iw : 0.f;
+    ih = ih > 0.f ? ih : 0.f;
+    const float inter = __fmul_rn(iw, ih);
+    const float ab = eval_area(b);
+    return __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(aa, ab), inter), 1e-12f));
+}
+
+__global__ __launch_bounds__(EVM_WAVES * 64) void eval_match_kernel(const EvalArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds_key[];
+    const int img = blockIdx.x, r = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    const EvalLds L = eval_lds(a.K, a.G);
+    char* lds = reinterpret_cast<char*>(lds_key);
+    f32x4* db = reinterpret_cast<f32x4*>(lds + L.db);
+    f32x4* gb = reinterpret_cast<f32x4*>(lds + L.gb);
+    float* ds = reinterpret_cast<float*>(lds + L.ds);
+    int16_t* dl = reinterpret_cast<int16_t*>(lds + L.dl);
+    int16_t* dr = reinterpret_cast<int16_t*>(lds + L.dr);
+    int16_t* gl = reinterpret_cast<int16_t*>(lds + L.gl);
+    uint16_t* ord = reinterpret_cast<uint16_t*>(lds + L.wave0 + wave * L.wave_bytes + L.ord);
+    uint16_t* walk = reinterpret_cast<uint16_t*>(lds + L.wave0 + wave * L.wave_bytes + L.walk);
+    uint16_t* used = reinterpret_cast<uint16_t*>(lds + L.wave0 + wave * L.wave_bytes + L.used);
+
+    const int kd_raw = a.counts[img];
+    if (kd_raw < 0) {   // a stale slab row: the image is skipped (block-uniform, before any barrier)
+        if (threadIdx.x == 0) atomicOr(&a.status[1], YMI_EVAL_STATUS_STALE_ROW);
+        return;
+    }
+    const int kd = kd_raw < a.K ? kd_raw : a.K;
+    const int gn_raw = a.gt_counts[img];
+    const int gn = gn_raw < 0 ? 0 : (gn_raw < a.G ? gn_raw : a.G);
+    const float lo = a.lo[r], hi = a.hi[r];
+    const int64_t drow = (int64_t)img * a.K, grow = (int64_t)img * a.G, orow = ((int64_t)r * a.N + img) * a.K;
+
+    // ---- stage the image; count its non-ignored ground truths ----
+    bool bad = false;
+    for (int j = threadIdx.x; j < kd; j += EVM_WAVES * 64) {
+        db[j] = *reinterpret_cast<const f32x4*>(a.boxes + (drow + j) * 4);
+        ds[j] = a.scores[drow + j];
+        const int64_t l = a.labels[drow + j];
+        const bool ok = l >= 0 && l < a.C;
+        dl[j] = ok ? (int16_t)l : (int16_t)-1;
+        bad |= !ok;
+    }
+    for (int g = threadIdx.x; g < gn; g += EVM_WAVES * 64) {
+        const f32x4 b = *reinterpret_cast<const f32x4*>(a.gt_boxes + (grow + g) * 4);
+        gb[g] = b;
+        const int l = a.gt_labels[grow + g];
+        const bool ok = l >= 0 && l < a.C;
+        bad |= !ok;
+        int16_t v = -1;
+        if (ok) {
+            const float ar = eval_area(b);
+            const bool ign = ar < lo || ar > hi;
+            v = (int16_t)(l | (ign ? EVM_IGN : 0));
+            if (!ign) atomicAdd(&a.n_gt[r * a.C + l], 1);
+        }
+        gl[g] = v;
+    }
+    if (bad) atomicOr(&a.status[1], YMI_EVAL_STATUS_BAD_LABEL);
+    __syncthreads();
+
+    // ---- rank within (image, class): detections of the class that sort before this one (score descending, slab order among equals, NaN last) ----
+    for (int j = threadIdx.x; j < kd; j += EVM_WAVES * 64) {
+        const int l = dl[j];
+        int rk = -1;
+        if (l >= 0) {
+            const float s = ds[j];
+            const bool s_nan = s != s;   // a total order, as the host's stable argsort of -score has it: NaN scores last, in slab order among themselves
+            rk = 0;
+            for (int q = 0; q < kd; ++q) {
+                const float sq = ds[q];
+                const bool before = s_nan ? (sq == sq || q < j) : (sq > s || (sq == s && q < j));
+                rk += (dl[q] == l && before) ? 1 : 0;
+            }
+            if (a.max_dets > 0 && rk >= a.max_dets) rk = -1;
+        }
+        dr[j] = (int16_t)rk;
+        if (r == 0) a.rank[drow + j] = rk;
+        if (rk < 0) {   // takes no part: its flags are defined (0) all the same
+            a.tp[orow + j] = 0;
+            a.ig[orow + j] = 0;
+        }
+    }
+    __syncthreads();
+
+    // ---- the classes present, dealt to the waves in slab order of their rank-0 detections (wave-uniform from here on: no block barrier below) ----
+    int leader = 0;
+    for (int b0 = 0; b0 < kd; b0 += 64) {
+        uint64_t lead = __ballot(b0 + lane < kd && dr[b0 + lane < kd ? b0 + lane : 0] == 0);
+        while (lead) {
+            const int li = __ffsll((long long)lead) - 1;
+            lead &= lead - 1;
+            if ((leader++ & (EVM_WAVES - 1)) != wave) continue;
+            const int c = dl[b0 + li];
+
+            // the class's detections by rank, its ground truths by walk position
+            int nd = 0;
+            for (int b = 0; b < kd; b += 64) {
+                const int j = b + lane;
+                const bool m = j < kd && dl[j] == c && dr[j] >= 0;
+                if (m) ord[dr[j]] = (uint16_t)j;
+                nd += __popcll(__ballot(m));
+            }
+            int nn = 0;
+            for (int b = 0; b < gn; b += 64) {
+                const int g = b + lane;
+                const bool m = g < gn && gl[g] == c;
+                const uint64_t mm = __ballot(m);
+                if (m) walk[nn + __popcll(mm & lt)] = (uint16_t)g;
+                nn += __popcll(mm);
+            }
+            int ngc = nn;
+            for (int b = 0; b < gn; b += 64) {
+                const int g = b + lane;
+                const bool m = g < gn && gl[g] == (c | EVM_IGN);
+                const uint64_t mm = __ballot(m);
+                if (m) walk[ngc + __popcll(mm & lt)] = (uint16_t)g;
+                ngc += __popcll(mm);
+            }
+            for (int p = lane; p < ngc; p += 64) used[p] = 0;
+            __builtin_amdgcn_wave_barrier();   // ord / walk: written by one lane, read by the others
+
+            for (int k = 0; k < nd; ++k) {
+                const int j = ord[k];
+                const f32x4 bd = db[j];
+                const float ad = eval_area(bd);
+                const bool d_out = ad < lo || ad > hi;
+                uint64_t best[YMI_EVAL_MAX_THRS];
+#pragma unroll
+                for (int t = 0; t < YMI_EVAL_MAX_THRS; ++t) best[t] = 0ull;
+                for (int p = lane; p < ngc; p += 64) {
+                    const float iou = eval_iou(bd, ad, gb[walk[p]]);
+                    const unsigned u = used[p];
+                    const uint64_t key = ((uint64_t)(p < nn ? 1 : 0) << 63) | ((uint64_t)__float_as_uint(iou) << 16) | (uint64_t)p;
+#pragma unroll
+                    for (int t = 0; t < YMI_EVAL_MAX_THRS; ++t)
+                        if (t < a.T && !((u >> t) & 1u) && iou >= a.thr[t] && key > best[t]) best[t] = key;
+                }
+                unsigned tpw = 0, igw = 0;
+#pragma unroll
+                for (int t = 0; t < YMI_EVAL_MAX_THRS; ++t) {
+                    if (t >= a.T) continue;
+                    uint64_t kb = best[t];
+                    const uint64_t has = __ballot(kb != 0ull);
+                    if (has == 0ull) {
+                        if (d_out) igw |= 1u << t;
+                        continue;
+                    }
+                    if (has & (has - 1)) {
+#pragma unroll
+                        for (int o = 32; o >= 1; o >>= 1) {
+                            const uint64_t other = __shfl_xor(kb, o, 64);
+                            kb = other > kb ? other : kb;
+                        }
+                    } else {
+                        kb = __shfl(kb, __ffsll((long long)has) - 1, 64);
+                    }
+                    const int p = (int)(kb & 0xffffull);
+                    if ((p & 63) == lane) used[p] = (uint16_t)(used[p] | (1u << t));   // read back by this lane only (its own positions)
+                    if (kb >> 63) tpw |= 1u << t; else igw |= 1u << t;
+                }
+                if (lane == 0) {
+                    a.tp[orow + j] = (uint16_t)tpw;
+                    a.ig[orow + j] = (uint16_t)igw;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();   // the next class rewrites ord / walk
+        }
+    }
+}
+
+static int eval_match_launch(const ymi_eval_desc* d, hipStream_t s) {
+    YMI_REQUIRE(d != nullptr, "ymi_eval_match: null descriptor");
+    YMI_REQUIRE(d->n >= 0 && d->k >= 0 && d->k <= YMI_EVAL_MAX_PER_IMAGE && d->g >= 0 && d->g <= YMI_EVAL_MAX_PER_IMAGE,
+                "ymi_eval_match: n=%d k=%d g=%d out of range (k, g <= %d per image)", d->n, d->k, d->g, YMI_EVAL_MAX_PER_IMAGE);
+    YMI_REQUIRE(d->num_thrs >= 1 && d->num_thrs <= YMI_EVAL_MAX_THRS, "ymi_eval_match: %d thresholds (1 .. %d)", d->num_thrs, YMI_EVAL_MAX_THRS);
+    YMI_REQUIRE(d->num_rngs >= 1 && d->num_rngs <= YMI_EVAL_MAX_RNGS, "ymi_eval_match: %d area ranges (1 .. %d)", d->num_rngs, YMI_EVAL_MAX_RNGS);
+    YMI_REQUIRE(d->num_classes >= 1 && d->num_classes <= 4096, "ymi_eval_match: num_classes=%d (1 .. 4096)", d->num_classes);
+    YMI_REQUIRE(d->max_dets >= 0, "ymi_eval_match: max_dets=%d (0 = no cut)", d->max_dets);
+    EvalArgs a;
+    for (int t = 0; t < YMI_EVAL_MAX_THRS; ++t) a.thr[t] = INFINITY;
+    for (int t = 0; t < d->num_thrs; ++t) {
+        YMI_REQUIRE(d->thrs[t] > 0.0 && d->thrs[t] <= 1.0, "ymi_eval_match: threshold %d = %g outside (0, 1]", t, d->thrs[t]);
+        const double tq = d->thrs[t] < 1.0 - 1e-10 ? d->thrs[t] : 1.0 - 1e-10;   // min(t, 1 - 1e-10) of the host loop
+        float f = (float)tq;
+        if ((double)f < tq) f = nextafterf(f, INFINITY);   // the smallest fp32 not below it: (double)iou >= tq  <=>  iou >= f
+        a.thr[t] = f;
+    }
+    for (int r = 0; r < YMI_EVAL_MAX_RNGS; ++r) {
+        a.lo[r] = r < d->num_rngs ? d->area_rng[r][0] : 0.f;
+        a.hi[r] = r < d->num_rngs ? d->area_rng[r][1] : 0.f;
+    }
+    if (d->n == 0) return YMI_OK;
+    YMI_REQUIRE(d->counts && d->gt_counts && d->tp && d->ig && d->rank && d->n_gt && d->status, "ymi_eval_match: null buffer");
+    YMI_REQUIRE(d->k == 0 || (d->boxes && d->scores && d->labels), "ymi_eval_match: null detection buffer");
+    YMI_REQUIRE(d->g == 0 || (d->gt_boxes && d->gt_labels), "ymi_eval_match: null ground-truth buffer");
+    a.boxes = d->boxes; a.scores = d->scores; a.labels = d->labels; a.counts = d->counts;
+    a.gt_boxes = d->gt_boxes; a.gt_labels = d->gt_labels; a.gt_counts = d->gt_counts;
+    a.tp = d->tp; a.ig = d->ig; a.rank = d->rank; a.n_gt = d->n_gt; a.status = d->status;
+    a.N = d->n; a.K = d->k; a.G = d->g; a.T = d->num_thrs; a.R = d->num_rngs; a.C = d->num_classes; a.max_dets = d->max_dets;
+    const size_t lds = (size_t)eval_lds(d->k, d->g).total;
+    if (lds > 64 * 1024) { const int rc_lds = allow_big_lds((const void*)eval_match_kernel, (int)lds); if (rc_lds != YMI_OK) return rc_lds; }
+    hipLaunchKernelGGL(eval_match_kernel, dim3(d->n, d->num_rngs), dim3(EVM_WAVES * 64), lds, s, a);
+    return check_launch("eval_match_kernel");
+}
+
 }  // namespace ymi
 
 using namespace ymi;
@@ -2076,6 +2345,8 @@ extern "C" int ymi_postprocess(const ymi_post_desc* d, void* stream) { return po
 extern "C" int ymi_post_begin(const ymi_post_desc* d, void* stream) { return post_begin_launch(d, (hipStream_t)stream); }
 extern "C" int ymi_post_finish(const ymi_post_desc* d, void* stream) { return post_finish_launch(d, (hipStream_t)stream); }
 extern "C" int ymi_post_decode_view(const ymi_post_desc* sink, const ymi_post_view* view, void* stream) { return post_decode_view_launch(sink, view, (hipStream_t)stream); }
+
+extern "C" int ymi_eval_match(const ymi_eval_desc* d, void* stream) { return eval_match_launch(d, (hipStream_t)stream); }
 
 extern "C" int64_t ymi_nms_ws_bytes(int n) {
     if (n <= 0) n = 1;

@@ -62,6 +62,71 @@ def nms(boxes: Tensor, scores: Tensor, iou_threshold: float) -> Tensor:
     return keep[:k].to(torch.int64)
 
 
+def _launch_eval_match(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, gt_boxes: Tensor, gt_labels: Tensor, gt_counts: Tensor, num_classes: int,
+                       iou_thrs, area_rngs, max_dets, tp: Optional[Tensor] = None, ig: Optional[Tensor] = None, rank: Optional[Tensor] = None,
+                       n_gt: Optional[Tensor] = None, status: Optional[Tensor] = None):
+    """One ymi_eval_match launch on the current stream, without a synchronisation: -> (tp, ig, rank, n_gt, status).  Output buffers handed in are written in place
+    (n_gt is added to, status[1] ORed into: the caller zeroed them once); missing ones are allocated (tp / ig / n_gt / status zeroed, rank filled with -1)."""
+    lib = _lib.load(require_gpu=True)
+    if not all(t.is_cuda for t in (boxes, scores, labels, counts, gt_boxes, gt_labels, gt_counts)):
+        raise YmiError("match_detections runs on an MI355X only (no CPU fallback)")
+    n, k = int(scores.shape[0]), int(scores.shape[1])
+    g = int(gt_labels.shape[1])
+    if tuple(boxes.shape) != (n, k, 4) or tuple(labels.shape) != (n, k) or tuple(counts.shape) != (n,):
+        raise YmiError(f"match_detections: expected the slab (N,K,4) / (N,K) / (N,K) / (N), got {tuple(boxes.shape)} {tuple(scores.shape)} {tuple(labels.shape)} {tuple(counts.shape)}")
+    if tuple(gt_boxes.shape) != (n, g, 4) or tuple(gt_counts.shape) != (n,):
+        raise YmiError(f"match_detections: expected ground truth (N,G,4) / (N,G) / (N), got {tuple(gt_boxes.shape)} {tuple(gt_labels.shape)} {tuple(gt_counts.shape)}")
+    if iou_thrs is None:
+        from .utils.metrics import COCO_IOU_THRS as iou_thrs   # numpy's linspace(.5, .95, 10): the host evaluator's own grid (metrics imports ops lazily too)
+    thrs = [float(t) for t in iou_thrs]
+    rngs = [(float("-inf"), float("inf"))] if area_rngs is None else [(float(lo), float(hi)) for lo, hi in area_rngs]
+    dev = boxes.device
+    d = _lib.EvalDesc()
+    d.n, d.k, d.g, d.num_thrs, d.num_rngs = n, k, g, len(thrs), len(rngs)
+    d.max_dets, d.num_classes = (0 if max_dets is None else int(max_dets)), int(num_classes)
+    for i, t in enumerate(thrs[:_lib.EVAL_MAX_THRS]):
+        d.thrs[i] = t
+    for i, (lo, hi) in enumerate(rngs[:_lib.EVAL_MAX_RNGS]):
+        d.area_rng[i][0], d.area_rng[i][1] = lo, hi
+    nr = max(min(len(rngs), _lib.EVAL_MAX_RNGS), 1)
+    tp = torch.zeros(nr, n, k, device=dev, dtype=torch.int16) if tp is None else tp      # uint16 words (bit t per threshold) in int16 storage
+    ig = torch.zeros(nr, n, k, device=dev, dtype=torch.int16) if ig is None else ig
+    rank = torch.full((n, k), -1, device=dev, dtype=torch.int32) if rank is None else rank
+    n_gt = torch.zeros(nr, max(int(num_classes), 1), device=dev, dtype=torch.int32) if n_gt is None else n_gt
+    status = torch.zeros(4, device=dev, dtype=torch.int32) if status is None else status
+    ins = [boxes.detach().to(torch.float32).contiguous(), scores.detach().to(torch.float32).contiguous(), labels.detach().to(torch.int64).contiguous(),
+           counts.detach().to(torch.int32).contiguous(), gt_boxes.detach().to(torch.float32).contiguous(), gt_labels.detach().to(torch.int32).contiguous(),
+           gt_counts.detach().to(torch.int32).contiguous()]
+    d.boxes, d.scores, d.labels, d.counts, d.gt_boxes, d.gt_labels, d.gt_counts = [t.data_ptr() for t in ins]
+    for t, shape, dt in ((tp, (nr, n, k), torch.int16), (ig, (nr, n, k), torch.int16), (rank, (n, k), torch.int32), (n_gt, (nr, int(num_classes)), torch.int32)):
+        if not t.is_cuda or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise YmiError(f"match_detections: an output buffer must be a contiguous device tensor of shape {shape} and dtype {dt}")
+    d.tp, d.ig, d.rank, d.n_gt, d.status = tp.data_ptr(), ig.data_ptr(), rank.data_ptr(), n_gt.data_ptr(), status.data_ptr()
+    check(lib.ymi_eval_match(C.byref(d), _lib.stream_ptr()), "ymi_eval_match")
+    return tp, ig, rank, n_gt, status
+
+
+def _raise_eval_status(bits: int) -> None:
+    if bits & _lib.EVAL_STATUS_STALE_ROW:
+        raise ValueError("the slab still holds a stale shard: take PendingDetections.gathered() (it resolves the second round) first")
+    if bits & _lib.EVAL_STATUS_BAD_LABEL:
+        raise ValueError("a detection or ground-truth label lies outside [0, num_classes)")
+
+
+def match_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, gt_boxes: Tensor, gt_labels: Tensor, gt_counts: Tensor, num_classes: int,
+                     iou_thrs: Optional[Sequence[float]] = None, area_rngs: Optional[Sequence[Sequence[float]]] = None, max_dets: Optional[int] = None):
+    """The greedy matching of the COCO detection protocol on the MI355X (ymi_eval_match, include/yolort_amd.h): the detection slab (boxes (N,K,4), scores (N,K), labels
+    (N,K) int64, counts (N)) exactly as `PendingDetections.gathered()` / `dist.all_gather_slab` return it against padded ground truth (gt_boxes (N,G,4), gt_labels (N,G),
+    gt_counts (N)) -> (tp, ig, rank, n_gt): tp / ig (R,N,K) int16 holding uint16 words with bit t per IoU threshold, rank (N,K) int32 (the position within the
+    (image, class) score order -- descending, ties in slab order, NaN scores last --, -1 = takes no part), n_gt (R,C) int32 non-ignored ground truths per class.  iou_thrs: at most 16 thresholds in (0, 1] (None: COCO's
+    0.50:0.05:0.95); area_rngs: at most 4 (lo, hi) pairs (None: one range that ignores nothing); max_dets: per (image, class), None = no cut.  K, G <= 1024.  Exactly the
+    flags of yolort_amd.utils.metrics.coco_ap's matching loop.  Raises ValueError for a stale slab row or a label outside [0, num_classes) (this reads the status word:
+    one synchronisation; GpuDetectionEvaluator defers it to compute()).  No CPU fallback."""
+    tp, ig, rank, n_gt, status = _launch_eval_match(boxes, scores, labels, counts, gt_boxes, gt_labels, gt_counts, num_classes, iou_thrs, area_rngs, max_dets)
+    _raise_eval_status(int(status[1].item()))
+    return tp, ig, rank, n_gt
+
+
 def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence[int]) -> List[Dict[str, Tensor]]:
     """Fixed (N,K,..) slab -> the reference's List[Dict] with keys in its order (box_head.py:427)."""
     out = []
