@@ -91,6 +91,57 @@ int ymi_letterbox(const void* const* imgs, const int32_t* geom, int n, int in_dt
 #define YMI_VIEW_PAD 0.447f
 int ymi_scale_view(const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Detection crops: every detection of the slab cut out of its ORIGINAL image and resized to one fixed size, in one launch per batch -- the input of a
+ * second-stage classifier, a re-identification or OCR net, or a dataset of cut-outs.  Replaces the host loops of save_one_box (yolort/v5/utils/plots.py:545-558,
+ * reached from Detections.crop, yolort/v5/models/common.py:644) and of apply_classifier (yolort/v5/utils/general.py:691-723), one cv2.resize per box.
+ *   imgs[i]   HOST array of n device pointers, the images as ymi_letterbox takes them: planar CHW (3, h, w) of in_dtype YMI_F32 / YMI_F16 / YMI_BF16 in [0, 1] or
+ *             YMI_U8 (scaled by 1/255, a true division), or interleaved (h, w, 3) uint8 for YMI_U8_HWC
+ *   hw        HOST array {h, w} per image
+ *   boxes     device (n, k, 4) fp32 xyxy in original-image coordinates, counts device (n) int32: the slab exactly as the top-k kernel writes it.  Slots at or past
+ *             a count are never read; a count below 0 or above k is clamped and sets YMI_CROP_STATUS_BAD_COUNT
+ *   crops     device (cap, 3, out_h, out_w) planar NCHW of out_dtype (YMI_F16 / YMI_BF16 / YMI_F32); index device (cap, 6) int32; total device int32[2]
+ * Rectangle of a detection, every operation a rounded fp32 one in the order torch evaluates save_one_box (plots.py:548-553 with general.py:397-400, :410-413, :507-510):
+ *   cx = (x1 + x2) / 2, cy = (y1 + y2) / 2, w = x2 - x1, h = y2 - y1;  square != 0: w = h = max(w, h);  w = w * gain + pad, h = h * gain + pad (two roundings each);
+ *   corners cx - w / 2, cy - h / 2, cx + w / 2, cy + h / 2, each truncated toward zero (.long()), then x clamped into [0, W], y into [0, H] (clip_coords).
+ * The crop is rows y1:y2 and columns x1:x2 of the image.  A non-finite coordinate (of the box or of a corner) gives the empty rectangle (0, 0, 0, 0); an empty
+ * rectangle (x2 <= x1 or y2 <= y1) gives an all-zero crop (not normalised) and keeps its row, so crops stay aligned with the detections; its index row reports the
+ * clipped corners as the reference computes them (e.g. {64, 0, 64, 14} for a box right of a 64-wide image).  gain / pad: save_one_box
+ * has 1.02 / 10, apply_classifier square, 1.3 / 30 -- but the reference pads in canvas pixels before scale_coords, this pads in image pixels (no parity claimed).
+ * Resize to (out_h, out_w): ymi_scale_view's arithmetic (ATen's upsample_bilinear2d, align_corners=False) INSIDE the rectangle -- scale = in / out rounded to fp32,
+ * source index ONE fmaf(scale, dst + 0.5, -0.5) clamped at 0, second tap clamped at the rectangle's last row / column (not the image's), four tap weights
+ * w_ij = fl(h_i * w_j), value fma(w11, v11, fma(w10, v10, fma(w00, v00, fl(w01 * v01)))) -- bit-identical to F.interpolate(mode="bilinear", align_corners=False) of
+ * the cut-out wherever the weights are powers of two (a rectangle of the output's size or twice it).  normalize != 0: then (v - mean[c]) / std[c], a rounded
+ * subtraction and a correctly rounded division.  ONE rounding to out_dtype.  (cv2.resize on uint8 uses fixed-point weights and differs in the last bit of a byte.)
+ * Order: image-major, the slab's order inside an image: row offset[i] + j holds detection j of image i, offset = the exclusive prefix of min(counts[i], k), computed
+ * on the device by every workgroup (crop_resize_kernel, csrc/preproc_pool.hip: a workgroup owns 256 x 4 adjacent pixels of one crop, 8- / 16-byte stores per plane
+ * where out_w % 4 == 0, scalar stores else).  index row = {image, detection, x1, y1, x2, y2} (the rectangle); total[0] = crops written = min(sum of the clamped
+ * counts, cap); total[1] = status: YMI_CROP_STATUS_CAPACITY when the sum exceeds cap (the first cap crops are written, the rest dropped),
+ * YMI_CROP_STATUS_BAD_COUNT.  Both words are WRITTEN by every call.  Rows at or beyond total[0] are not written, in crops or in index; nothing outside the two
+ * buffers and total is written.  More than 64 images go as several launches over image ranges that all read the whole counts array (offsets stay global).
+ * YMI_EINVAL: a null buffer (crops / index may be null only with cap 0, the inputs only with n 0), out_h or out_w < 1, cap < 0, n or k < 0, an unsupported dtype, normalize with a std of 0,
+ * gain / pad (or mean / std) not finite.  No allocation, no synchronisation: ordered on `stream`, may be captured.  ABI stays 6: one new struct, one new function.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_CROP_STATUS_CAPACITY 1  /* total[1] bit 0 */
+#define YMI_CROP_STATUS_BAD_COUNT 2 /* total[1] bit 1 */
+typedef struct ymi_crop_desc {
+    const void* const* imgs;
+    const int32_t* hw;
+    const float* boxes;
+    const int32_t* counts;
+    void* crops;
+    int32_t* index;
+    int32_t* total;
+    float mean[3], std[3];
+    float gain, pad;
+    int32_t n, k, cap;
+    int32_t out_h, out_w;
+    int32_t in_dtype, out_dtype;
+    int32_t square, normalize;
+    int32_t reserved;
+} ymi_crop_desc;
+int ymi_crop_resize(const ymi_crop_desc* d, void* stream);
+
 /* NCHW (n,c,h,w) -> NHWC view and back (module-level API edges; not on the fused path). */
 int ymi_nchw_to_nhwc(const void* x, int n, int c, int h, int w, int in_dtype, void* y, int y_cstride,
                      int c_pad, int out_dtype, void* stream);

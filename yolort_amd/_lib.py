@@ -122,6 +122,20 @@ class EvalDesc(C.Structure):
     ]
 
 
+CROP_STATUS_CAPACITY, CROP_STATUS_BAD_COUNT = 1, 2   # YMI_CROP_STATUS_*: bits of total[1]
+
+
+class CropDesc(C.Structure):
+    """ymi_crop_desc: the images (host arrays of device pointers and sizes), the detection slab, the outputs and the parameters of one ymi_crop_resize call"""
+    _fields_ = [
+        ("imgs", C.POINTER(C.c_void_p)), ("hw", C.POINTER(C.c_int32)), ("boxes", C.c_void_p), ("counts", C.c_void_p),
+        ("crops", C.c_void_p), ("index", C.c_void_p), ("total", C.c_void_p),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3), ("gain", C.c_float), ("pad", C.c_float),
+        ("n", C.c_int32), ("k", C.c_int32), ("cap", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("in_dtype", C.c_int32), ("out_dtype", C.c_int32), ("square", C.c_int32), ("normalize", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 VIEW_PAD = 0.447   # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
 TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
 
@@ -194,6 +208,7 @@ _SIGS = {
     "ymi_batched_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_eval_match": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p]),
+    "ymi_crop_resize": (C.c_int, [C.POINTER(CropDesc), C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

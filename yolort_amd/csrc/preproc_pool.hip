@@ -857,6 +857,160 @@ __global__ __launch_bounds__(1024) void spp_pool_f32_lds_kernel(float* buf, int 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Detection crops (ymi_crop_resize): every detection of the slab cut out of its ORIGINAL image and resized to one fixed size, planar NCHW, one launch per batch.
+// Replaces the host loops of save_one_box (yolort/v5/utils/plots.py:545-558, reached from Detections.crop, yolort/v5/models/common.py:644) and of apply_classifier
+// (yolort/v5/utils/general.py:691-723): rectangle = xyxy2xywh -> (square) -> * gain + pad -> xywh2xyxy -> .long() -> clip_coords in explicitly rounded fp32, resize =
+// scale_view_kernel's arithmetic inside the rectangle (the second tap clamps at the RECTANGLE's last row / column).
+// A workgroup owns 256 * PX adjacent output pixels of ONE crop slot (image, detection) and finds its row itself: every wave sums the clamped counts of the images
+// before its own with a 64-lane butterfly (n is small) -- no second launch, no LDS.  PX = 4: a thread owns four adjacent pixels of a row and stores 8 bytes
+// (16-bit types) or 16 bytes (fp32) per plane, a wave one contiguous 512-byte / 1-KiB run (a plane is contiguous, so runs continue across rows); PX = 1: the scalar
+// form for widths that are no multiple of 4.  Measured (profiles/crop_bench.txt): 1.04 TB/s written on the C2 detections at 224 x 224 fp16, a third of copy_view_kernel's
+// write rate -- NOT store-bound.  Supposed cause (from the code, not from counters): the issue of the 48 scalar gather loads a thread makes for its 24 output bytes, the
+// regime of letterbox_kernel above; staging the source rows in LDS as letterbox_tile2_kernel does is the untried next step.
+// ---------------------------------------------------------------------------------------------
+struct CropArgs {
+    const void* img[LB_MAX];   // images img_base .. img_base + img_n - 1
+    int hw[LB_MAX][2];
+    const float* boxes;
+    const int32_t* counts;
+    void* crops;
+    int32_t* index;
+    int32_t* total;
+    int n, img_base, img_n, k, cap, out_h, out_w, tiles, square, normalize;
+    float gain, pad, mean[3], std[3];
+};
+
+// the rectangle of one detection, r = {x1, y1, x2, y2}; false = nothing to cut: a non-finite coordinate (r all zero) or an empty rectangle (r = the clipped corners)
+__device__ __forceinline__ bool crop_rect(const float b[4], int H, int W, int square, float gain, float pad, int r[4]) {
+    r[0] = r[1] = r[2] = r[3] = 0;
+    const float lim = 3.0e38f;   // |v| <= lim is false for NaN and +-inf
+    if (!(fabsf(b[0]) <= lim && fabsf(b[1]) <= lim && fabsf(b[2]) <= lim && fabsf(b[3]) <= lim)) return false;
+    const float cx = __fdiv_rn(__fadd_rn(b[0], b[2]), 2.0f), cy = __fdiv_rn(__fadd_rn(b[1], b[3]), 2.0f);   // xyxy2xywh, general.py:397-400
+    float w = __fsub_rn(b[2], b[0]), h = __fsub_rn(b[3], b[1]);
+    if (square) { const float m = w > h ? w : h; w = m; h = m; }                                            // plots.py:550
+    w = __fadd_rn(__fmul_rn(w, gain), pad);                                                                  // plots.py:551
+    h = __fadd_rn(__fmul_rn(h, gain), pad);
+    const float hw2 = __fdiv_rn(w, 2.0f), hh2 = __fdiv_rn(h, 2.0f);
+    const float c[4] = {__fsub_rn(cx, hw2), __fsub_rn(cy, hh2), __fadd_rn(cx, hw2), __fadd_rn(cy, hh2)};     // xywh2xyxy, general.py:410-413
+    if (!(fabsf(c[0]) <= lim && fabsf(c[1]) <= lim && fabsf(c[2]) <= lim && fabsf(c[3]) <= lim)) return false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {   // .long() truncates toward zero, clip_coords clamps the integer into [0, W] / [0, H]: the same as this, for every finite value
+        const int hi = (i & 1) ? H : W;
+        r[i] = c[i] <= 0.f ? 0 : (c[i] >= (float)hi ? hi : (int)c[i]);
+    }
+    return r[2] > r[0] && r[3] > r[1];   // an empty rectangle keeps the clipped corners the reference gives it (the index reports them); its crop is all zero
+}
+
+// scale_view_kernel's source taps of destination index d: indices i0, i1 inside [0, n_in), weight l1 of i1
+__device__ __forceinline__ void crop_taps(float s, int d, int n_in, int& i0, int& i1, float& l1) {
+    float f = fmaf(s, (float)d + 0.5f, -0.5f);
+    f = f < 0.f ? 0.f : f;
+    i0 = (int)f;
+    i0 = i0 > n_in - 1 ? n_in - 1 : i0;
+    i1 = i0 + 1 > n_in - 1 ? n_in - 1 : i0 + 1;
+    l1 = f - (float)i0;
+    l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
+}
+
+template <int IDT, int ODT, int PX>
+__global__ __launch_bounds__(256) void crop_resize_kernel(const CropArgs a) {
+    const int kk = a.k > 0 ? a.k : 1;
+    const int slot = (int)(blockIdx.x / (unsigned)a.tiles), tile = (int)(blockIdx.x - (unsigned)slot * (unsigned)a.tiles);
+    const int li = slot / kk, det = slot - li * kk;
+    const int img = a.img_base + li;
+    // exclusive prefix of min(counts, k) at `img`, the grand total and the own count: lane l takes images l, l + 64, ...; wave-uniform trip count
+    int before = 0, all = 0, mine = 0, bad = 0;
+    const int lane = threadIdx.x & 63;
+    for (int i0 = 0; i0 < a.n; i0 += 64) {
+        const int i = i0 + lane;
+        const int c = i < a.n ? a.counts[i] : 0;
+        const int cc = c < 0 ? 0 : (c > a.k ? a.k : c);
+        bad |= (c != cc) ? 1 : 0;
+        all += cc;
+        before += i < img ? cc : 0;
+        mine += i == img ? cc : 0;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        before += __shfl_xor(before, m);
+        all += __shfl_xor(all, m);
+        mine += __shfl_xor(mine, m);
+        bad |= __shfl_xor(bad, m);
+    }
+    if (blockIdx.x == 0 && a.img_base == 0 && threadIdx.x == 0) {
+        a.total[0] = all < a.cap ? all : a.cap;
+        a.total[1] = (all > a.cap ? YMI_CROP_STATUS_CAPACITY : 0) | (bad ? YMI_CROP_STATUS_BAD_COUNT : 0);
+    }
+    if (li >= a.img_n || det >= mine) return;
+    const int row = before + det;
+    if (row >= a.cap) return;
+    const int H = a.hw[li][0], W = a.hw[li][1];
+    const float* bp = a.boxes + ((int64_t)img * a.k + det) * 4;
+    const float b[4] = {bp[0], bp[1], bp[2], bp[3]};
+    int r[4];
+    const bool any = crop_rect(b, H, W, a.square, a.gain, a.pad, r);
+    if (tile == 0 && threadIdx.x < 6) {
+        const int t = (int)threadIdx.x;
+        a.index[(int64_t)row * 6 + t] = t == 0 ? img : (t == 1 ? det : r[t - 2]);
+    }
+    const int wq = a.out_w / PX;
+    const int q = tile * 256 + (int)threadIdx.x;
+    if (q >= a.out_h * wq) return;
+    const int y = q / wq, x = (q - y * wq) * PX;
+    float v[PX][3];
+#pragma unroll
+    for (int p = 0; p < PX; ++p) v[p][0] = v[p][1] = v[p][2] = 0.f;
+    if (any) {
+        const int rh = r[3] - r[1], rw = r[2] - r[0];
+        const float sy = (float)rh / (float)a.out_h, sx = (float)rw / (float)a.out_w;
+        int y0, y1;
+        float ly1;
+        crop_taps(sy, y, rh, y0, y1, ly1);
+        const float ly0 = 1.f - ly1;
+        y0 += r[1];
+        y1 += r[1];
+        const int64_t plane = (int64_t)H * W;
+        const void* src = a.img[li];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) {
+            int x0, x1;
+            float lx1;
+            crop_taps(sx, x + p, rw, x0, x1, lx1);
+            const float lx0 = 1.f - lx1;
+            x0 += r[0];
+            x1 += r[0];
+            const float w00 = __fmul_rn(ly0, lx0), w01 = __fmul_rn(ly0, lx1), w10 = __fmul_rn(ly1, lx0), w11 = __fmul_rn(ly1, lx1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float p00 = load_elem<IDT>(src, src_index<IDT>(c, y0, x0, W, plane)), p01 = load_elem<IDT>(src, src_index<IDT>(c, y0, x1, W, plane));
+                const float p10 = load_elem<IDT>(src, src_index<IDT>(c, y1, x0, W, plane)), p11 = load_elem<IDT>(src, src_index<IDT>(c, y1, x1, W, plane));
+                float val = fmaf(w11, p11, fmaf(w10, p10, fmaf(w00, p00, __fmul_rn(w01, p01))));
+                if (a.normalize) val = __fdiv_rn(__fsub_rn(val, a.mean[c]), a.std[c]);
+                v[p][c] = val;
+            }
+        }
+    }
+    const int64_t oplane = (int64_t)a.out_h * a.out_w;
+    const int64_t o = (int64_t)row * 3 * oplane + (int64_t)q * PX;   // a plane is contiguous: pixel (y, x) is element y * out_w + x = q * PX
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if constexpr (PX == 4 && ODT == YMI_F32) {
+            const f32x4 w = {v[0][c], v[1][c], v[2][c], v[3][c]};
+            *reinterpret_cast<f32x4*>((float*)a.crops + o + c * oplane) = w;
+        } else if constexpr (PX == 4) {
+            u32x2 w;
+            w[0] = cvt_pk16<ODT>(f32x2{v[0][c], v[1][c]});
+            w[1] = cvt_pk16<ODT>(f32x2{v[2][c], v[3][c]});
+            *reinterpret_cast<u32x2*>((uint16_t*)a.crops + o + c * oplane) = w;
+        } else if constexpr (ODT == YMI_F32) {
+            ((float*)a.crops)[o + c * oplane] = v[0][c];
+        } else {
+            ((uint16_t*)a.crops)[o + c * oplane] = to16<ODT>(v[0][c]);
+        }
+    }
+}
+
 }  // namespace ymi
 
 using namespace ymi;
@@ -1033,4 +1187,74 @@ extern "C" int ymi_scale_view(const void* src, int n, int h, int w, void* dst, i
     else if (dtype == YMI_F16) hipLaunchKernelGGL((scale_view_kernel<YMI_F16>), grid, block, 0, s, src, n, h, w, dst, dh, dw, sh, sw, flip);
     else hipLaunchKernelGGL((scale_view_kernel<YMI_BF16>), grid, block, 0, s, src, n, h, w, dst, dh, dw, sh, sw, flip);
     return check_launch("scale_view_kernel");
+}
+
+template <int IDT>
+static int crop_dispatch(const CropArgs& a, int out_dtype, bool wide, unsigned blocks, hipStream_t s) {
+    dim3 grid(blocks), block(256);
+#define YMI_CROP(ODT_)                                                                     \
+    if (wide) hipLaunchKernelGGL((crop_resize_kernel<IDT, ODT_, 4>), grid, block, 0, s, a); \
+    else hipLaunchKernelGGL((crop_resize_kernel<IDT, ODT_, 1>), grid, block, 0, s, a);
+    switch (out_dtype) {
+        case YMI_F16: YMI_CROP(YMI_F16) break;
+        case YMI_BF16: YMI_CROP(YMI_BF16) break;
+        default: YMI_CROP(YMI_F32) break;
+    }
+#undef YMI_CROP
+    return check_launch("crop_resize_kernel");
+}
+
+extern "C" int ymi_crop_resize(const ymi_crop_desc* d, void* stream) {
+    YMI_REQUIRE(d != nullptr, "ymi_crop_resize: null descriptor");
+    YMI_REQUIRE(d->n >= 0 && d->k >= 0, "ymi_crop_resize: negative batch size %d or slab depth %d", d->n, d->k);
+    YMI_REQUIRE(d->total && (d->n == 0 || (d->imgs && d->hw && d->counts && (d->boxes || d->k == 0))), "ymi_crop_resize: null buffer (images, sizes, boxes, counts or total)");
+    YMI_REQUIRE(d->cap >= 0, "ymi_crop_resize: negative capacity %d", d->cap);
+    YMI_REQUIRE(d->cap == 0 || (d->crops && d->index), "ymi_crop_resize: null output buffer (crops or index) with capacity %d", d->cap);
+    YMI_REQUIRE(d->out_h >= 1 && d->out_w >= 1, "ymi_crop_resize: output size %d x %d below 1", d->out_h, d->out_w);
+    YMI_REQUIRE(d->in_dtype == YMI_F16 || d->in_dtype == YMI_BF16 || d->in_dtype == YMI_F32 || d->in_dtype == YMI_U8 || d->in_dtype == YMI_U8_HWC,
+                "ymi_crop_resize: unsupported in_dtype %d", d->in_dtype);
+    YMI_REQUIRE(d->out_dtype == YMI_F16 || d->out_dtype == YMI_BF16 || d->out_dtype == YMI_F32, "ymi_crop_resize: unsupported out_dtype %d (F16 / BF16 / F32)", d->out_dtype);
+    const float big = 3.0e38f;
+    YMI_REQUIRE(fabsf(d->gain) <= big && fabsf(d->pad) <= big, "ymi_crop_resize: gain and pad must be finite");
+    if (d->normalize)
+        for (int c = 0; c < 3; ++c)
+            YMI_REQUIRE(fabsf(d->mean[c]) <= big && fabsf(d->std[c]) <= big && d->std[c] != 0.f, "ymi_crop_resize: std[%d] is 0 (or mean / std not finite)", c);
+    for (int i = 0; i < d->n; ++i) {
+        YMI_REQUIRE(d->imgs[i] != nullptr, "ymi_crop_resize: image %d is null", i);
+        YMI_REQUIRE(d->hw[2 * i] >= 0 && d->hw[2 * i + 1] >= 0 && (int64_t)d->hw[2 * i] * d->hw[2 * i + 1] < ((int64_t)1 << 31), "ymi_crop_resize: image %d has a bad size %d x %d", i, d->hw[2 * i], d->hw[2 * i + 1]);
+    }
+    YMI_REQUIRE((int64_t)d->n * d->k < ((int64_t)1 << 31) && (int64_t)d->out_h * d->out_w < ((int64_t)1 << 31), "ymi_crop_resize: n * k or out_h * out_w does not fit 31 bits");
+    // four pixels per thread where a row is a whole number of 4-pixel groups and the stores are aligned; YOLORT_AMD_CROP=pixel: the one-pixel-per-thread form (A/B runs)
+    const char* env = getenv("YOLORT_AMD_CROP");
+    const size_t esz = d->out_dtype == YMI_F32 ? 4 : 2;
+    const bool wide = d->out_w % 4 == 0 && ((uintptr_t)d->crops & (4 * esz - 1)) == 0 && !(env && !strcmp(env, "pixel"));
+    const int64_t tiles = ((int64_t)d->out_h * (d->out_w / (wide ? 4 : 1)) + 255) / 256;
+    for (int base = 0; base < d->n || base == 0; base += LB_MAX) {   // every launch reads the WHOLE counts array: row offsets are global; the first one writes total[]
+        CropArgs a;
+        a.img_n = d->n - base < LB_MAX ? d->n - base : LB_MAX;
+        for (int i = 0; i < a.img_n; ++i) {
+            a.img[i] = d->imgs[base + i];
+            a.hw[i][0] = d->hw[2 * (base + i)];
+            a.hw[i][1] = d->hw[2 * (base + i) + 1];
+        }
+        a.boxes = d->boxes; a.counts = d->counts; a.crops = d->crops; a.index = d->index; a.total = d->total;
+        a.n = d->n; a.img_base = base; a.k = d->k; a.cap = d->cap; a.out_h = d->out_h; a.out_w = d->out_w; a.tiles = (int)tiles;
+        a.square = d->square ? 1 : 0; a.normalize = d->normalize ? 1 : 0;
+        a.gain = d->gain; a.pad = d->pad;
+        for (int c = 0; c < 3; ++c) { a.mean[c] = d->mean[c]; a.std[c] = d->std[c]; }
+        int64_t blocks = (int64_t)a.img_n * d->k * tiles;
+        if (d->cap == 0 || blocks == 0) blocks = base == 0 ? 1 : 0;   // nothing to cut: one workgroup of the first launch still writes total[]
+        if (blocks == 0) continue;
+        YMI_REQUIRE(blocks < ((int64_t)1 << 31), "ymi_crop_resize: %lld workgroups in one launch", (long long)blocks);
+        int rc;
+        switch (d->in_dtype) {
+            case YMI_F32: rc = crop_dispatch<YMI_F32>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
+            case YMI_F16: rc = crop_dispatch<YMI_F16>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
+            case YMI_BF16: rc = crop_dispatch<YMI_BF16>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
+            case YMI_U8: rc = crop_dispatch<YMI_U8>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
+            default: rc = crop_dispatch<YMI_U8_HWC>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
+        }
+        if (rc != YMI_OK) return rc;
+    }
+    return YMI_OK;
 }

@@ -160,6 +160,36 @@ class YOLOv5(nn.Module):
         images = self.collate_images(x, image_loader)
         return self.forward(images, canvas=canvas)
 
+    @torch.no_grad()
+    def crop(self, images: List[Tensor], detections: Optional[List[Dict[str, Tensor]]] = None, size: Tuple[int, int] = (224, 224), **kw: Any) -> List[Tensor]:
+        """The detected objects cut out of the original images and resized to `size`: per image a (len(detections[i]), 3, size[0], size[1]) tensor in the order of its
+        detections -- the device form of the reference's `Detections.crop(save=False)` (yolort/v5/models/common.py:644 -> save_one_box, yolort/v5/utils/plots.py:545-558).
+        `images`: the list forward() takes; `detections`: its List[Dict] for these images (None: forward() runs first).  The boxes are packed into a slab, cut by ONE
+        launch (`yolort_amd.ops.crop_detections`, whose keyword arguments -- gain, pad, square, mean, std, dtype -- pass through) and split by the counts after one
+        synchronisation.  forward() / predict() themselves are untouched."""
+        from .. import ops
+        images = [images[i] for i in range(len(images))]
+        if detections is None:
+            detections = self.forward(images)
+        if len(detections) != len(images):
+            raise ValueError(f"crop: {len(detections)} detection dicts for {len(images)} images")
+        if "capacity" in kw:
+            raise ValueError("crop: the capacity is the number of detections")
+        n = len(images)
+        lens = [int(d["boxes"].shape[0]) for d in detections]
+        k = max(lens + [1])
+        dev = images[0].device if n else torch.device("cuda")
+        slab = torch.zeros((n, k, 4), device=dev, dtype=torch.float32)
+        for i, d in enumerate(detections):
+            if lens[i]:
+                slab[i, : lens[i]] = d["boxes"].to(device=dev, dtype=torch.float32)
+        counts = torch.tensor(lens, dtype=torch.int32).to(dev)
+        crops, _, total = ops.crop_detections(images, slab, counts, size, capacity=sum(lens), **kw)
+        written, status = total.tolist()   # the one synchronisation
+        if status != 0 or written != sum(lens):
+            raise YmiError(f"crop: the kernel wrote {written} of {sum(lens)} crops (status {status})")
+        return list(torch.split(crops, lens)) if n else []
+
     def default_loader(self, img_path: str) -> Tensor:
         """RGB uint8 image as decoded, (H, W, 3); the permute and the /255 of the reference (yolov5.py:218-228) are fused into
         the letterbox kernel's interleaved-uint8 path (decode stays on the host, PIL)."""

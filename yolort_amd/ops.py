@@ -127,6 +127,69 @@ def match_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tens
     return tp, ig, rank, n_gt
 
 
+def crop_detections(images: Sequence[Tensor], boxes: Tensor, counts: Tensor, size, *, gain: float = 1.02, pad: float = 10, square: bool = False,
+                    mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None, dtype: torch.dtype = torch.float16, capacity: Optional[int] = None):
+    """Every detection of the slab cut out of its original image and resized to `size` = (out_h, out_w), on the MI355X in one launch per batch (ymi_crop_resize,
+    include/yolort_amd.h): the device form of the reference's `Detections.crop()` / save_one_box (yolort/v5/utils/plots.py:545-558) and of apply_classifier's cut-outs
+    (yolort/v5/utils/general.py:691-723).  images: the list `YOLOv5.forward` takes -- (3, h, w) float in [0, 1] or uint8, or interleaved (h, w, 3) uint8, one dtype and
+    layout per batch, sizes may differ; boxes (n, K, 4) xyxy in original-image coordinates and counts (n,): the slab form.  -> (crops, index, total), device tensors of
+    full capacity and NO synchronisation: crops (capacity, 3, out_h, out_w) of `dtype` (fp16 / bf16 / fp32), image-major in the slab's order; index (capacity, 6) int32
+    rows {image, detection, x1, y1, x2, y2} (the integer rectangle that was cut); total int32[2] = {crops written, status bits _lib.CROP_STATUS_CAPACITY /
+    _lib.CROP_STATUS_BAD_COUNT}.  Rows at or beyond total[0] are uninitialised.  capacity defaults to n * K.
+    The rectangle is save_one_box's, in its fp32 order: box -> centre and size, (square: both sides the larger one), side * gain + pad, corners truncated toward zero
+    and clipped to the image; an empty rectangle gives an all-zero crop that keeps its row (its index row holds the clipped corners), a non-finite box likewise with the rectangle (0, 0, 0, 0).  The defaults are save_one_box's; apply_classifier's
+    recipe is square=True, gain=1.3, pad=30, size=(224, 224) -- but the reference pads in CANVAS pixels before scale_coords while this op pads in image pixels, so that
+    recipe is not claimed as parity.  The resize is F.interpolate(mode="bilinear", align_corners=False) of the cut-out (bit for bit where the weights are powers of
+    two, a few fp32 ulps elsewhere), optionally followed by (v - mean[c]) / std[c]; cv2.resize on uint8 uses fixed-point weights and differs in the last bit of a byte."""
+    from .models.transform import YOLOTransform
+    lib = _lib.load(require_gpu=True)
+    images = [images[i] for i in range(len(images))]
+    n = len(images)
+    if not boxes.is_cuda or not counts.is_cuda or not all(im.is_cuda for im in images):
+        raise YmiError("crop_detections runs on an MI355X only (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4 or tuple(counts.shape) != (n,):
+        raise YmiError(f"crop_detections: expected the slab (n, K, 4) / (n,) for {n} images, got {tuple(boxes.shape)} {tuple(counts.shape)}")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise YmiError(f"crop_detections: dtype must be float16, bfloat16 or float32, got {dtype}")
+    if (mean is None) != (std is None):
+        raise ValueError("crop_detections: mean and std go together")
+    out_h, out_w = int(size[0]), int(size[1])
+    k = int(boxes.shape[1])
+    cap = n * k if capacity is None else int(capacity)
+    hwc = False
+    if n:
+        kinds = {(im.dtype, YOLOTransform.is_hwc(im)) for im in images}
+        if len(kinds) != 1:
+            raise YmiError("all images of a batch must share one dtype and layout")
+        hwc = YOLOTransform.is_hwc(images[0])
+        for im in images:
+            if im.dim() != 3 or (im.shape[0] != 3 and not hwc):
+                raise ValueError(f"images are expected to be (3, H, W) tensors (or (H, W, 3) uint8), got {tuple(im.shape)}")
+        images = [im if im.is_contiguous() else im.contiguous() for im in images]
+    dev = boxes.device
+    d = _lib.CropDesc()
+    ptrs = (C.c_void_p * max(n, 1))(*[im.data_ptr() for im in images])
+    hw = (C.c_int32 * max(2 * n, 1))(*[v for im in images for v in YOLOTransform.image_hw(im)])
+    b = boxes.detach().to(torch.float32).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    crops = torch.empty((max(cap, 0), 3, max(out_h, 0), max(out_w, 0)), device=dev, dtype=dtype)
+    index = torch.empty((max(cap, 0), 6), device=dev, dtype=torch.int32)
+    total = torch.empty(2, device=dev, dtype=torch.int32)
+    d.imgs, d.hw = C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(hw, C.POINTER(C.c_int32))
+    d.boxes, d.counts, d.crops, d.index, d.total = b.data_ptr(), c.data_ptr(), crops.data_ptr(), index.data_ptr(), total.data_ptr()
+    d.gain, d.pad, d.square, d.normalize = float(gain), float(pad), 1 if square else 0, 0 if mean is None else 1
+    if mean is not None:
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("crop_detections: mean and std have one value per channel")
+        for i in range(3):
+            d.mean[i], d.std[i] = float(mean[i]), float(std[i])
+    d.n, d.k, d.cap, d.out_h, d.out_w = n, k, cap, out_h, out_w
+    d.in_dtype = _lib.YMI_U8_HWC if hwc else (_lib.dtype_code(images[0].dtype) if n else _lib.YMI_F32)
+    d.out_dtype = _lib.dtype_code(dtype)
+    check(lib.ymi_crop_resize(C.byref(d), _lib.stream_ptr()), "ymi_crop_resize")
+    return crops, index, total
+
+
 def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence[int]) -> List[Dict[str, Tensor]]:
     """Fixed (N,K,..) slab -> the reference's List[Dict] with keys in its order (box_head.py:427)."""
     out = []
