@@ -222,8 +222,8 @@ __global__ __launch_bounds__(256) void letterbox_copy_kernel(const LetterboxArgs
 // each thread writes TWO pixels = one 16-byte store (a wave covers 1 KiB of a canvas row).  Same arithmetic as
 // letterbox_kernel, operation for operation: results are bit-identical.
 constexpr int LB_TH = 4, LB_TW = 128;
-constexpr int LB_RPW_DEFAULT = 4;
-constexpr int LB_CG_DEFAULT = 1;    // 128-pixel column groups per tile of letterbox_tile2_kernel   // rows per wave of letterbox_tile2_kernel (tile = 4 * RPW rows x 128 columns)
+constexpr int LB_RPW_DEFAULT = 4;   // rows per wave of letterbox_tile2_kernel (tile = 4 * RPW rows x 128 columns)
+constexpr int LB_CG_DEFAULT = 1;    // 128-pixel column groups per tile of letterbox_tile2_kernel
 
 struct LetterboxTileArgs {
     LetterboxArgs base;
