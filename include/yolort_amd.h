@@ -142,6 +142,75 @@ typedef struct ymi_crop_desc {
 } ymi_crop_desc;
 int ymi_crop_resize(const ymi_crop_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Annotated images: every detection of the slab drawn into its ORIGINAL image -- outline, label background, label text -- IN PLACE, in one launch per batch.
+ * Replaces the host loop of Detections.render() / show() / save() (yolort/v5/models/common.py:575-652): per detection one Annotator.box_label
+ * (yolort/v5/utils/plots.py:98-159) = three drawing calls, with the images leaving the device and coming back around it.
+ *   imgs[i]   HOST array of n device pointers, the images as ymi_letterbox / ymi_crop_resize take them, WRITTEN in place: planar CHW (3, h, w) of in_dtype YMI_F32 /
+ *             YMI_F16 / YMI_BF16 in [0, 1] or YMI_U8, or interleaved (h, w, 3) uint8 for YMI_U8_HWC
+ *   hw        HOST array {h, w} per image;  lw, fs: HOST arrays, per image the outline width and the integer font scale, each in [1, 65535]
+ *   boxes     device (n, k, 4) fp32 xyxy in original-image coordinates, scores (n, k) fp32, labels (n, k) int64, counts (n) int32: the slab as ymi_eval_desc takes it
+ *   names     device (num_classes, YMI_RENDER_NAME_STRIDE) uint8: a length byte in 0..27 (a larger one counts as 27), then the bytes; null: the class index in decimal
+ *   colors    device (m, 3) uint8 RGB; a detection has colors[label % m];  txt_color: RGB of the text, each in 0..255
+ * THE DRAWING RULE (integer arithmetic throughout; x, y are pixel indices of the image):
+ *   Corners   X0, Y0, X1, Y1 = the box's x1, y1, x2, y2 truncated toward zero (the int(box[i]) of the reference's cv2 branch, the truncation ymi_crop_resize uses).
+ *             A detection draws NOTHING when a coordinate is not finite or has magnitude >= 2^24, or X1 < X0, or Y1 < Y0.
+ *   Outline   of width lw: the pixels with X0 <= x <= X1, Y0 <= y <= Y1 and (x < X0 + lw or x > X1 - lw or y < Y0 + lw or y > Y1 - lw), clipped to the image.  This is
+ *             PIL.ImageDraw.rectangle(width=lw, outline=...) -- the call of the reference's PIL branch -- wherever 2 * lw <= min(X1 - X0, Y1 - Y0) + 1; for thicker
+ *             outlines this rule fills the box, while PIL paints outside it: the rule is the contract there.
+ *   Label     (draw_labels != 0) text = the class name, then (draw_conf != 0) ' ' and the score as %.2f; L characters, L == 0 draws no label.  Cells of 6 x 11 pixels
+ *             magnified fs times by pixel replication: w = 6 * fs * L, h = 11 * fs.  Placement is box_label's PIL branch: outside = (Y0 - h >= 0), ty = Y0 - h if
+ *             outside, else Y0.  Background: the inclusive rectangle [X0, ty, X0 + w + 1, ty + h + 1] in the box colour, clipped to the image.  Glyphs: pixel (x, y) of
+ *             [X0, X0 + w) x [ty, ty + h) belongs to character (x - X0) / (6 * fs), column ((x - X0) % (6 * fs)) / fs, row (y - ty) / fs; a set bit gives txt_color.
+ *   Pixel     the LOWEST slot whose outline or label background covers the pixel decides: txt_color where a glyph bit of THAT detection is set, its box colour
+ *             elsewhere -- the result of the reference's draw order (reversed(pred); outline, background, text per box).  A pixel no detection covers is not written.
+ *   Colour    uint8 images store the byte; float images store byte / 255, a true division rounded ONCE to the dtype (for all 256 bytes the fp32 quotient rounded to
+ *             fp16 / bf16 equals the directly rounded one).
+ *   Score     a finite score in [0, 1] prints as the exact value of the fp32 score times 100 rounded to nearest, ties to even, "d.dd" -- what Python's
+ *             f"{float(score):.2f}" prints (0.125 -> 0.12, 0.375 -> 0.38); the product is exact in fp64 (24 + 7 bits).  -0.0 compares as 0 and prints "-0.00", as
+ *             Python does.  Any other score (NaN, negative, above 1, infinite) prints "?.??".
+ *   Names     a byte outside 32..126 draws as '?'.  ASCII only, at most 27 bytes.
+ *   Font      95 cells of 6 x 11 bits from Pillow's built-in bitmap font, one getmask() per character (csrc/render_font.hpp, tools/make_render_font.py).  The TEXT HAS
+ *             NO PARITY WITH THE REFERENCE: that needs a downloaded Arial.ttf or cv2's Hershey strokes; outline and background geometry are the reference's PIL branch.
+ *   Counts    slots at or past a count are never read; a count above k is taken as k and sets YMI_RENDER_STATUS_BAD_COUNT; a negative count (a stale slab row,
+ *             YMI_SLAB_STALE) skips the image and sets YMI_RENDER_STATUS_STALE_ROW; a label outside [0, num_classes) skips that detection and sets
+ *             YMI_RENDER_STATUS_BAD_LABEL.  status is ONE int32 the kernel ORs bits into; the caller zeroes it.
+ *   Writes    nothing outside the images' own h * w * 3 elements, and no pixel that no detection covers.
+ * render_kernel (csrc/preproc_pool.hip) is a GATHER, no races and no atomics on pixels: a workgroup owns a tile of 64 x 16 pixels of one image, compacts the
+ * detections whose drawing extent (outline united with label background) meets the tile into an LDS list in slot order (wave ballot + prefix), returns WITHOUT
+ * touching the image when the list is empty, and otherwise lets every pixel take its colour from the first list entry that covers it.  A thread owns four adjacent
+ * pixels (12 contiguous bytes interleaved, 4 / 8 / 16 bytes per plane; scalar stores where w % 4 != 0, the view is misaligned or only some of the four are covered).
+ * Ragged sizes: the grid is the sum of the images' tiles, found from a by-value table; more than 64 images go as several launches.
+ * YMI_EINVAL: a null buffer (names may be null; everything may be with n 0), k > YMI_RENDER_MAX_K, n or k < 0, an lw or fs outside [1, 65535], m < 1, num_classes < 1,
+ * a txt_color outside 0..255, an unsupported dtype, a null image or a negative size.  No allocation, no synchronisation: ordered on `stream`, may be captured.
+ * ABI stays 6: one new struct, one new function.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_RENDER_MAX_K 1024
+#define YMI_RENDER_NAME_STRIDE 28
+#define YMI_RENDER_STATUS_BAD_COUNT 1 /* status bit 0 */
+#define YMI_RENDER_STATUS_STALE_ROW 2 /* status bit 1 */
+#define YMI_RENDER_STATUS_BAD_LABEL 4 /* status bit 2 */
+typedef struct ymi_render_desc {
+    void* const* imgs;
+    const int32_t* hw;
+    const int32_t* lw;
+    const int32_t* fs;
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const uint8_t* names;
+    const uint8_t* colors;
+    int32_t* status;
+    int32_t m;
+    int32_t txt_color[3];
+    int32_t num_classes, in_dtype;
+    int32_t draw_labels, draw_conf;
+    int32_t n, k;
+    int32_t reserved;
+} ymi_render_desc;
+int ymi_render(const ymi_render_desc* d, void* stream);
+
 /* NCHW (n,c,h,w) -> NHWC view and back (module-level API edges; not on the fused path). */
 int ymi_nchw_to_nhwc(const void* x, int n, int c, int h, int w, int in_dtype, void* y, int y_cstride,
                      int c_pad, int out_dtype, void* stream);

@@ -136,7 +136,22 @@ class CropDesc(C.Structure):
     ]
 
 
-VIEW_PAD = 0.447   # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
+RENDER_MAX_K, RENDER_NAME_STRIDE = 1024, 28   # YMI_RENDER_MAX_K, YMI_RENDER_NAME_STRIDE
+RENDER_STATUS_BAD_COUNT, RENDER_STATUS_STALE_ROW, RENDER_STATUS_BAD_LABEL = 1, 2, 4   # YMI_RENDER_STATUS_*: bits of the status word
+
+
+class RenderDesc(C.Structure):
+    """ymi_render_desc: the images (host arrays of device pointers, sizes, outline widths and font scales), the detection slab, the name and colour tables and the
+    flags of one ymi_render call"""
+    _fields_ = [
+        ("imgs", C.POINTER(C.c_void_p)), ("hw", C.POINTER(C.c_int32)), ("lw", C.POINTER(C.c_int32)), ("fs", C.POINTER(C.c_int32)),
+        ("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p), ("names", C.c_void_p), ("colors", C.c_void_p), ("status", C.c_void_p),
+        ("m", C.c_int32), ("txt_color", C.c_int32 * 3), ("num_classes", C.c_int32), ("in_dtype", C.c_int32), ("draw_labels", C.c_int32), ("draw_conf", C.c_int32),
+        ("n", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+VIEW_PAD = 0.447  # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
 TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
 
 
@@ -209,6 +224,7 @@ _SIGS = {
     "ymi_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_eval_match": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p]),
     "ymi_crop_resize": (C.c_int, [C.POINTER(CropDesc), C.c_void_p]),
+    "ymi_render": (C.c_int, [C.POINTER(RenderDesc), C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

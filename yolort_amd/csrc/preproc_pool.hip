@@ -1011,6 +1011,250 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Annotated images (ymi_render): every detection of the slab drawn into its ORIGINAL image in place -- outline, label background, label text -- one launch per batch.
+// Replaces the host loop of Detections.render() (yolort/v5/models/common.py:575-652): per detection one Annotator.box_label (yolort/v5/utils/plots.py:98-159).
+// THE DRAWING RULE is the contract and is written out in include/yolort_amd.h (ymi_render); in short, all in integers:
+//   corners X0, Y0, X1, Y1 = the box truncated toward zero; nothing is drawn for a non-finite coordinate, a magnitude >= 2^24, X1 < X0 or Y1 < Y0;
+//   outline: X0 <= x <= X1, Y0 <= y <= Y1 and (x < X0 + lw or x > X1 - lw or y < Y0 + lw or y > Y1 - lw)   (PIL's rectangle(width=lw) where 2 lw <= min side + 1);
+//   label of L characters in 6 x 11 cells magnified fs times: w = 6 fs L, h = 11 fs, ty = Y0 - h if Y0 - h >= 0 else Y0; background [X0, ty, X0 + w + 1, ty + h + 1]
+//   inclusive; glyph pixel (x, y) of [X0, X0 + w) x [ty, ty + h): character (x - X0) / (6 fs), column ((x - X0) % (6 fs)) / fs, row (y - ty) / fs;
+//   the LOWEST slot whose outline or background covers a pixel decides it: txt_color on a glyph bit of that detection, colors[label % m] elsewhere;
+//   score text: rint((double)score * 100) (exact product, ties to even) as d.dd for a score in [0, 1] ("-0.00" for -0.0, like Python), "?.??" for any other.
+// The text has NO parity with the reference (that needs a downloaded Arial.ttf or cv2's Hershey strokes): the cells are Pillow's built-in bitmap font (render_font.hpp).
+// A GATHER, no races and no atomics on pixels: a workgroup owns one RD_TW x RD_TH = 64 x 16 tile of one image.  Phase 1: its 256 threads walk the image's detections
+// below the count, 256 slots a pass, and compact those whose drawing extent (outline united with label background) meets the tile into an LDS list IN SLOT ORDER
+// (ballot + popcount inside a wave, the four wave totals through LDS); label, score and name length are read only for boxes whose outline or widest possible label
+// reaches the tile.  Tile 0 of an image reports its status bits.  A tile with an empty list returns without reading or writing the image: untouched tiles cost no
+// memory traffic.  Phase 2: a thread owns four adjacent pixels of a row and walks the list from the lowest slot up until all four are decided; covered pixels are
+// stored -- all four at once (12 contiguous bytes interleaved, 4 / 8 / 16 bytes per plane) where w % 4 == 0, the view is aligned and all four are covered, one by one
+// otherwise.  Ragged sizes: the grid is the sum of the images' tiles, a workgroup finds image and tile in the by-value table; > LB_MAX images: several launches.
+// ---------------------------------------------------------------------------------------------
+#include "render_font.hpp"
+
+constexpr int RD_TW = 64, RD_TH = 16;
+constexpr int RD_MAX_L = 27 + 1 + 5;   // the longest label: a 27-byte name, ' ', "-0.00"  (names = null: at most 10 digits)
+struct RenderArgs {
+    void* img[LB_MAX];        // images img_base .. img_base + img_n - 1
+    int hw[LB_MAX][2];
+    int lwfs[LB_MAX][2];      // outline width, font scale
+    int tile_end[LB_MAX];     // inclusive prefix of the images' tile counts (>= 1 tile per image: tile 0 reports the status bits)
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const uint8_t* names;
+    const uint8_t* colors;
+    int32_t* status;
+    int img_base, img_n, k, m, num_classes, draw_labels, draw_conf;
+    uint32_t txt;             // r | g << 8 | b << 16
+};
+struct RenderEntry {          // 32 bytes of LDS per listed detection
+    int x0, y0, x1, y1;
+    int ty;                   // top row of the label
+    int label;
+    uint32_t info;            // L | name length << 8 | score code << 16 (hundredths 0..100, 101: "?.??") | negative zero << 24
+    uint32_t rgb;
+};
+
+// character `ci` of the label of entry e (ci < L)
+__device__ __forceinline__ int render_char(const RenderEntry& e, int ci, const uint8_t* names) {
+    const int nl = (int)((e.info >> 8) & 0xff);
+    int ch;
+    if (ci < nl) {
+        if (names) {
+            ch = names[(int64_t)e.label * YMI_RENDER_NAME_STRIDE + 1 + ci];
+        } else {   // the class index in decimal: digit nl - 1 - ci counted from the units
+            int v = e.label;
+            for (int i = nl - 1 - ci; i > 0; --i) v /= 10;
+            ch = '0' + v % 10;
+        }
+    } else {
+        const int code = (int)((e.info >> 16) & 0xff), neg = (int)((e.info >> 24) & 1);
+        int t = ci - nl - 1;   // -1: the blank
+        if (t < 0) return ' ';
+        if (neg) {
+            if (t == 0) return '-';
+            --t;
+        }
+        if (t == 1) return '.';
+        if (code > 100) return '?';
+        ch = '0' + (t == 0 ? code / 100 : (t == 2 ? code / 10 % 10 : code % 10));
+    }
+    return (ch < 32 || ch > 126) ? '?' : ch;
+}
+
+template <int IDT>
+__global__ __launch_bounds__(256) void render_kernel(const RenderArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lb_sm[];
+    RenderEntry* list = reinterpret_cast<RenderEntry*>(lb_sm);          // k entries
+    int* wcnt = reinterpret_cast<int*>(lb_sm + (size_t)a.k * sizeof(RenderEntry));   // the four wave totals of a pass
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int li = 0;
+    for (int i = 0; i < a.img_n - 1; ++i) li += (int)blockIdx.x >= a.tile_end[i] ? 1 : 0;   // block-uniform
+    const int tile = (int)blockIdx.x - (li ? a.tile_end[li - 1] : 0);
+    const int H = a.hw[li][0], W = a.hw[li][1], lw = a.lwfs[li][0], fs = a.lwfs[li][1];
+    const int tiles_x = W > 0 ? (W + RD_TW - 1) / RD_TW : 1;
+    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+    const int tx0 = txi * RD_TW, ty0 = tyi * RD_TH, tx1 = tx0 + RD_TW - 1, ty1 = ty0 + RD_TH - 1;   // the tile, inclusive
+    const int img = a.img_base + li;
+    const int craw = a.counts[img];
+    const int cnt = craw < 0 ? 0 : (craw > a.k ? a.k : craw);
+    int bits = craw < 0 ? YMI_RENDER_STATUS_STALE_ROW : (craw > a.k ? YMI_RENDER_STATUS_BAD_COUNT : 0);
+    const int cw = 6 * fs, chh = 11 * fs;   // a character cell on the image
+    const float lim = 16777216.0f;
+    int nlist = 0;
+    // ---- phase 1: the tile's list, in slot order ----
+    for (int base = 0; base < cnt; base += 256) {
+        const int s = base + tid;
+        bool hit = false;
+        RenderEntry e = {};
+        if (s < cnt) {
+            const float* bp = a.boxes + ((int64_t)img * a.k + s) * 4;
+            const float b0 = bp[0], b1 = bp[1], b2 = bp[2], b3 = bp[3];
+            const bool finite = fabsf(b0) < lim && fabsf(b1) < lim && fabsf(b2) < lim && fabsf(b3) < lim;   // false for NaN and +-inf
+            e.x0 = finite ? (int)b0 : 0; e.y0 = finite ? (int)b1 : 0; e.x1 = finite ? (int)b2 : -1; e.y1 = finite ? (int)b3 : -1;
+            const bool drawn = finite && e.x1 >= e.x0 && e.y1 >= e.y0;
+            e.ty = e.y0 - chh >= 0 ? e.y0 - chh : e.y0;
+            // the outline's rectangle, or the background of the longest possible label, reaches the tile (tile 0 reads every label: it reports the bad ones)
+            const bool box_in = e.x0 <= tx1 && e.x1 >= tx0 && e.y0 <= ty1 && e.y1 >= ty0;
+            const bool lab_in = a.draw_labels && e.x0 <= tx1 && e.x0 + cw * RD_MAX_L + 1 >= tx0 && e.ty <= ty1 && e.ty + chh + 1 >= ty0;
+            if (tile == 0 || (drawn && (box_in || lab_in))) {
+                const int64_t lab = a.labels[(int64_t)img * a.k + s];
+                if (lab < 0 || lab >= (int64_t)a.num_classes) {
+                    bits |= YMI_RENDER_STATUS_BAD_LABEL;
+                } else if (drawn) {
+                    e.label = (int)lab;
+                    int L = 0, nl = 0, code = 0, neg = 0;
+                    if (a.draw_labels) {
+                        if (a.names) {
+                            nl = a.names[lab * YMI_RENDER_NAME_STRIDE];
+                            nl = nl > YMI_RENDER_NAME_STRIDE - 1 ? YMI_RENDER_NAME_STRIDE - 1 : nl;
+                        } else {
+                            nl = 1;
+                            for (int v = (int)lab; v >= 10; v /= 10) ++nl;
+                        }
+                        L = nl;
+                        if (a.draw_conf) {
+                            const float sc = a.scores[(int64_t)img * a.k + s];
+                            if (sc >= 0.f && sc <= 1.f) {
+                                code = (int)rint((double)sc * 100.0);   // the product is exact: 24 + 7 bits
+                                neg = (int)(__float_as_uint(sc) >> 31);   // -0.0
+                            } else {
+                                code = 101;
+                            }
+                            L += 1 + neg + 4;
+                        }
+                    }
+                    e.info = (uint32_t)L | ((uint32_t)nl << 8) | ((uint32_t)code << 16) | ((uint32_t)neg << 24);
+                    const uint8_t* cp = a.colors + (lab % a.m) * 3;
+                    e.rgb = (uint32_t)cp[0] | ((uint32_t)cp[1] << 8) | ((uint32_t)cp[2] << 16);
+                    hit = box_in || (L > 0 && e.x0 <= tx1 && e.x0 + cw * L + 1 >= tx0 && e.ty <= ty1 && e.ty + chh + 1 >= ty0);
+                }
+            }
+        }
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) wcnt[wv] = __popcll(mask);
+        __syncthreads();
+        int off = nlist + __popcll(mask & ((1ull << lane) - 1ull));
+        for (int w = 0; w < 4; ++w) {
+            off += w < wv ? wcnt[w] : 0;
+            nlist += wcnt[w];
+        }
+        if (hit) list[off] = e;
+        __syncthreads();   // the list is complete up to nlist, and wcnt is free for the next pass
+    }
+    if (tile == 0) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) bits |= __shfl_xor(bits, m);
+        if (lane == 0 && bits) atomicOr(a.status, (int32_t)bits);
+    }
+    if (nlist == 0) return;   // nothing meets this tile: the image is neither read nor written
+    // ---- phase 2: four adjacent pixels per thread ----
+    const int y = ty0 + (tid >> 4), x = tx0 + (tid & 15) * 4;
+    if (y >= H || x >= W) return;
+    uint32_t col[4] = {0u, 0u, 0u, 0u};
+    unsigned found = 0;
+    const unsigned want = x + 3 < W ? 0xfu : ((1u << (W - x)) - 1u);
+    for (int i = 0; i < nlist && found != want; ++i) {
+        const RenderEntry e = list[i];
+        const int L = (int)(e.info & 0xff);
+        const int lx1 = e.x0 + cw * L + 1, ly1 = e.ty + chh + 1;   // the label background's last column and row
+        const bool row_box = y >= e.y0 && y <= e.y1, row_lab = L > 0 && y >= e.ty && y <= ly1;
+        if (!row_box && !row_lab) continue;
+        const bool row_edge = y < e.y0 + lw || y > e.y1 - lw;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int xp = x + p;
+            if ((found >> p) & 1u || !((want >> p) & 1u)) continue;
+            const bool in_box = row_box && xp >= e.x0 && xp <= e.x1 && (row_edge || xp < e.x0 + lw || xp > e.x1 - lw);
+            const bool in_lab = row_lab && xp >= e.x0 && xp <= lx1;
+            if (!in_box && !in_lab) continue;
+            uint32_t c = e.rgb;
+            if (in_lab && xp < lx1 - 1 && y < ly1 - 1) {   // inside [X0, X0 + w) x [ty, ty + h): a glyph cell
+                const int dx = xp - e.x0, ci = dx / cw;
+                const int gc = (dx - ci * cw) / fs, gr = (y - e.ty) / fs;
+                const int ch = render_char(e, ci, a.names);
+                if ((YMI_RENDER_FONT[(ch - 32) * YMI_RENDER_FONT_H + gr] >> (YMI_RENDER_FONT_W - 1 - gc)) & 1) c = a.txt;
+            }
+            col[p] = c;
+            found |= 1u << p;
+        }
+    }
+    if (!found) return;
+    constexpr int ESZ = (IDT == YMI_F32) ? 4 : ((IDT == YMI_F16 || IDT == YMI_BF16) ? 2 : 1);
+    const int64_t plane = (int64_t)H * W;
+    const bool vec = found == 0xfu && (W & 3) == 0 && ((uintptr_t)a.img[li] & (uintptr_t)(4 * ESZ - 1)) == 0;
+    if constexpr (IDT == YMI_U8_HWC) {
+        uint8_t* o = (uint8_t*)a.img[li] + ((int64_t)y * W + x) * 3;
+        if (vec) {   // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+            uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+            o4[0] = (col[0] & 0xffffffu) | (col[1] << 24);
+            o4[1] = ((col[1] >> 8) & 0xffffu) | (col[2] << 16);
+            o4[2] = ((col[2] >> 16) & 0xffu) | (col[3] << 8);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if ((found >> p) & 1u) {
+                    o[3 * p] = (uint8_t)col[p]; o[3 * p + 1] = (uint8_t)(col[p] >> 8); o[3 * p + 2] = (uint8_t)(col[p] >> 16);
+                }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int64_t o = c * plane + (int64_t)y * W + x;
+            uint32_t by[4];
+            float v[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                by[p] = (col[p] >> (8 * c)) & 0xffu;
+                v[p] = __fdiv_rn((float)by[p], 255.0f);   // a true division; rounded to fp16 / bf16 it equals the directly rounded quotient for all 256 bytes
+            }
+            if constexpr (IDT == YMI_U8) {
+                uint8_t* q = (uint8_t*)a.img[li] + o;
+                if (vec) *reinterpret_cast<uint32_t*>(q) = by[0] | (by[1] << 8) | (by[2] << 16) | (by[3] << 24);
+                else
+                    for (int p = 0; p < 4; ++p) if ((found >> p) & 1u) q[p] = (uint8_t)by[p];
+            } else if constexpr (IDT == YMI_F32) {
+                float* q = (float*)a.img[li] + o;
+                if (vec) *reinterpret_cast<f32x4*>(q) = f32x4{v[0], v[1], v[2], v[3]};
+                else
+                    for (int p = 0; p < 4; ++p) if ((found >> p) & 1u) q[p] = v[p];
+            } else {
+                uint16_t* q = (uint16_t*)a.img[li] + o;
+                if (vec) {
+                    u32x2 w2;
+                    w2[0] = cvt_pk16<IDT>(f32x2{v[0], v[1]});
+                    w2[1] = cvt_pk16<IDT>(f32x2{v[2], v[3]});
+                    *reinterpret_cast<u32x2*>(q) = w2;
+                } else {
+                    for (int p = 0; p < 4; ++p) if ((found >> p) & 1u) q[p] = to16<IDT>(v[p]);
+                }
+            }
+        }
+    }
+}
+
 }  // namespace ymi
 
 using namespace ymi;
@@ -1254,6 +1498,58 @@ extern "C" int ymi_crop_resize(const ymi_crop_desc* d, void* stream) {
             case YMI_U8: rc = crop_dispatch<YMI_U8>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
             default: rc = crop_dispatch<YMI_U8_HWC>(a, d->out_dtype, wide, (unsigned)blocks, (hipStream_t)stream); break;
         }
+        if (rc != YMI_OK) return rc;
+    }
+    return YMI_OK;
+}
+
+extern "C" int ymi_render(const ymi_render_desc* d, void* stream) {
+    YMI_REQUIRE(d != nullptr, "ymi_render: null descriptor");
+    YMI_REQUIRE(d->n >= 0 && d->k >= 0, "ymi_render: negative batch size %d or slab depth %d", d->n, d->k);
+    YMI_REQUIRE(d->k <= YMI_RENDER_MAX_K, "ymi_render: slab depth %d above YMI_RENDER_MAX_K = %d", d->k, YMI_RENDER_MAX_K);
+    if (d->n == 0) return YMI_OK;
+    YMI_REQUIRE(d->imgs && d->hw && d->lw && d->fs && d->boxes && d->scores && d->labels && d->counts && d->colors && d->status,
+                "ymi_render: null buffer (images, sizes, lw, fs, boxes, scores, labels, counts, colors or status)");
+    YMI_REQUIRE(d->m >= 1 && d->num_classes >= 1, "ymi_render: %d colours (m) or %d classes, below 1", d->m, d->num_classes);
+    YMI_REQUIRE(d->in_dtype == YMI_F16 || d->in_dtype == YMI_BF16 || d->in_dtype == YMI_F32 || d->in_dtype == YMI_U8 || d->in_dtype == YMI_U8_HWC,
+                "ymi_render: unsupported in_dtype %d (interleaved images are uint8 only)", d->in_dtype);
+    for (int c = 0; c < 3; ++c) YMI_REQUIRE(d->txt_color[c] >= 0 && d->txt_color[c] <= 255, "ymi_render: txt_color[%d] = %d outside 0..255", c, d->txt_color[c]);
+    for (int i = 0; i < d->n; ++i) {
+        YMI_REQUIRE(d->imgs[i] != nullptr, "ymi_render: image %d is null", i);
+        YMI_REQUIRE(d->hw[2 * i] >= 0 && d->hw[2 * i + 1] >= 0 && (int64_t)d->hw[2 * i] * d->hw[2 * i + 1] < ((int64_t)1 << 31), "ymi_render: image %d has a bad size %d x %d", i, d->hw[2 * i], d->hw[2 * i + 1]);
+        YMI_REQUIRE(d->lw[i] >= 1 && d->lw[i] <= 65535, "ymi_render: lw[%d] = %d outside [1, 65535]", i, d->lw[i]);
+        YMI_REQUIRE(d->fs[i] >= 1 && d->fs[i] <= 65535, "ymi_render: fs[%d] = %d outside [1, 65535]", i, d->fs[i]);
+    }
+    const size_t lds = (size_t)d->k * sizeof(RenderEntry) + 4 * sizeof(int);
+    for (int base = 0; base < d->n; base += LB_MAX) {
+        RenderArgs a;
+        a.img_n = d->n - base < LB_MAX ? d->n - base : LB_MAX;
+        int64_t blocks = 0;
+        for (int i = 0; i < a.img_n; ++i) {
+            const int h = d->hw[2 * (base + i)], w = d->hw[2 * (base + i) + 1];
+            a.img[i] = d->imgs[base + i];
+            a.hw[i][0] = h;
+            a.hw[i][1] = w;
+            a.lwfs[i][0] = d->lw[base + i];
+            a.lwfs[i][1] = d->fs[base + i];
+            const int64_t t = (int64_t)cdiv(w, RD_TW) * cdiv(h, RD_TH);
+            blocks += t > 0 ? t : 1;   // an empty image keeps one workgroup: tile 0 reports the status bits of its count
+            a.tile_end[i] = (int)blocks;
+            YMI_REQUIRE(blocks < ((int64_t)1 << 31), "ymi_render: %lld workgroups in one launch", (long long)blocks);
+        }
+        a.boxes = d->boxes; a.scores = d->scores; a.labels = d->labels; a.counts = d->counts; a.names = d->names; a.colors = d->colors; a.status = d->status;
+        a.img_base = base; a.k = d->k; a.m = d->m; a.num_classes = d->num_classes; a.draw_labels = d->draw_labels ? 1 : 0; a.draw_conf = d->draw_conf ? 1 : 0;
+        a.txt = (uint32_t)d->txt_color[0] | ((uint32_t)d->txt_color[1] << 8) | ((uint32_t)d->txt_color[2] << 16);
+        dim3 grid((unsigned)blocks), block(256);
+        hipStream_t s = (hipStream_t)stream;
+        switch (d->in_dtype) {
+            case YMI_F32: hipLaunchKernelGGL((render_kernel<YMI_F32>), grid, block, lds, s, a); break;
+            case YMI_F16: hipLaunchKernelGGL((render_kernel<YMI_F16>), grid, block, lds, s, a); break;
+            case YMI_BF16: hipLaunchKernelGGL((render_kernel<YMI_BF16>), grid, block, lds, s, a); break;
+            case YMI_U8: hipLaunchKernelGGL((render_kernel<YMI_U8>), grid, block, lds, s, a); break;
+            default: hipLaunchKernelGGL((render_kernel<YMI_U8_HWC>), grid, block, lds, s, a); break;
+        }
+        const int rc = check_launch("render_kernel");
         if (rc != YMI_OK) return rc;
     }
     return YMI_OK;

@@ -2,7 +2,7 @@
 (reference yolort/models/yolov5.py:19-297)."""
 from __future__ import annotations
 
-from typing import Any, Callable, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor, nn
@@ -189,6 +189,40 @@ class YOLOv5(nn.Module):
         if status != 0 or written != sum(lens):
             raise YmiError(f"crop: the kernel wrote {written} of {sum(lens)} crops (status {status})")
         return list(torch.split(crops, lens)) if n else []
+
+    @torch.no_grad()
+    def render(self, images: List[Tensor], detections: Optional[List[Dict[str, Tensor]]] = None, names: Optional[Sequence[str]] = None, **kw: Any) -> List[Tensor]:
+        """The images with their detections drawn in -- outline, label background, "name score" text per box, the first detection on top: the device form of the
+        reference's `Detections.render()` (yolort/v5/models/common.py:575-652 -> Annotator.box_label, yolort/v5/utils/plots.py:98-159).  `images`: the list forward()
+        takes; `detections`: its List[Dict] for these images (None: forward() runs first); `names`: the class names (None: the class index is drawn).  The dicts are
+        packed into a slab, drawn by ONE launch (`yolort_amd.ops.draw_detections`, whose keyword arguments -- colors, line_width, font_scale, labels_on, conf,
+        txt_color, inplace -- pass through) and ONE status word is read back.  Copies are drawn on unless inplace=True.  forward() / predict() themselves are untouched."""
+        from .. import ops
+        images = [images[i] for i in range(len(images))]
+        if detections is None:
+            detections = self.forward(images)
+        if len(detections) != len(images):
+            raise ValueError(f"render: {len(detections)} detection dicts for {len(images)} images")
+        n = len(images)
+        if n == 0:
+            return []
+        lens = [int(d["boxes"].shape[0]) for d in detections]
+        k = max(lens + [1])
+        dev = images[0].device
+        boxes = torch.zeros((n, k, 4), device=dev, dtype=torch.float32)
+        scores = torch.zeros((n, k), device=dev, dtype=torch.float32)
+        labels = torch.zeros((n, k), device=dev, dtype=torch.int64)
+        for i, d in enumerate(detections):
+            if lens[i]:
+                boxes[i, : lens[i]] = d["boxes"].to(device=dev, dtype=torch.float32)
+                scores[i, : lens[i]] = d["scores"].to(device=dev, dtype=torch.float32)
+                labels[i, : lens[i]] = d["labels"].to(device=dev, dtype=torch.int64)
+        counts = torch.tensor(lens, dtype=torch.int32).to(dev)
+        out, status = ops.draw_detections(images, boxes, scores, labels, counts, names=names, **kw)
+        status = int(status.item())   # the one synchronisation
+        if status != 0:
+            raise YmiError(f"render: the kernel reports status {status} (bad count 1, stale row 2, label outside the names 4)")
+        return out
 
     def default_loader(self, img_path: str) -> Tensor:
         """RGB uint8 image as decoded, (H, W, 3); the permute and the /255 of the reference (yolov5.py:218-228) are fused into

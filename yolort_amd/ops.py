@@ -190,6 +190,111 @@ def crop_detections(images: Sequence[Tensor], boxes: Tensor, counts: Tensor, siz
     return crops, index, total
 
 
+# The default colours of draw_detections, the project's own: 20 hues in steps of 7 / 20 of the colour circle (neighbouring classes far apart), saturation 0.85 / 0.6
+# and value 1.0 / 0.8 alternating -- RGB.  A detection of class c has DEFAULT_COLORS[c % 20].
+DEFAULT_COLORS = ((255, 38, 38), (102, 255, 117), (65, 31, 204), (204, 118, 82), (38, 255, 125), (178, 102, 255), (204, 135, 31), (82, 204, 167), (212, 38, 255), (255, 240, 102),
+                  (31, 204, 204), (204, 82, 192), (212, 255, 38), (102, 209, 255), (204, 31, 135), (143, 204, 82), (38, 125, 255), (255, 102, 148), (65, 204, 31), (82, 94, 204))
+_render_tables: Dict[tuple, Tensor] = {}   # (kind, content, device) -> device table: built once per names tuple / palette and device
+
+
+def render_name_table(names: Sequence[str]) -> Tensor:
+    """(len(names), 28) uint8 on the host, ymi_render's name table: a length byte, then the ASCII bytes (a character outside ASCII becomes '?'); at most 27 bytes a name"""
+    rows = torch.zeros((len(names), _lib.RENDER_NAME_STRIDE), dtype=torch.uint8)
+    for i, name in enumerate(names):
+        raw = str(name).encode("ascii", "replace")
+        if len(raw) > _lib.RENDER_NAME_STRIDE - 1:
+            raise ValueError(f"draw_detections: the name of class {i} has {len(raw)} bytes (at most {_lib.RENDER_NAME_STRIDE - 1})")
+        rows[i, 0] = len(raw)
+        rows[i, 1: 1 + len(raw)] = torch.tensor(list(raw), dtype=torch.uint8)
+    return rows
+
+
+def _render_table(kind: str, content: tuple, dev: torch.device) -> Tensor:
+    key = (kind, content, str(dev))
+    t = _render_tables.get(key)
+    if t is None:
+        host = render_name_table(content) if kind == "names" else torch.tensor(content, dtype=torch.uint8).reshape(-1, 3)
+        t = _render_tables[key] = host.to(dev)
+    return t
+
+
+def render_defaults(h: int, w: int):
+    """(lw, fs) the reference gives an h x w image: Annotator's line width max(round(sum(im.shape) / 2 * 0.003), 2) on an (h, w, 3) array and its PIL branch's font
+    size max(round(sum(im.size) / 2 * 0.035), 12) in units of the 11-pixel cell (yolort/v5/utils/plots.py:98-117)"""
+    return max(round((h + w + 3) / 2 * 0.003), 2), max(1, round(max(round((h + w) / 2 * 0.035), 12) / 11))
+
+
+def draw_detections(images: Sequence[Tensor], boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, *, names: Optional[Sequence[str]] = None,
+                    colors: Optional[Sequence[Sequence[int]]] = None, line_width=None, font_scale=None, labels_on: bool = True, conf: bool = True,
+                    txt_color: Sequence[int] = (255, 255, 255), inplace: bool = False):
+    """Every detection of the slab drawn into its original image -- outline, label background, label text -- on the MI355X in one launch per batch (ymi_render,
+    include/yolort_amd.h, where the drawing rule is written out): the device form of the reference's `Detections.render()` (yolort/v5/models/common.py:575-652), a host
+    loop of one `Annotator.box_label` (yolort/v5/utils/plots.py:98-159) per box.  images: the list `YOLOv5.forward` takes -- (3, h, w) float in [0, 1] or uint8, or
+    interleaved (h, w, 3) uint8, one dtype and layout per batch, sizes may differ; boxes (n, K, 4) xyxy in original-image coordinates, scores (n, K), labels (n, K),
+    counts (n,): the slab form, K <= 1024.  -> (images, status): the annotated images (the inputs themselves with inplace=True -- they must be contiguous --, clones
+    otherwise; the kernel always draws in place) and the int32 status word on the device (_lib.RENDER_STATUS_BAD_COUNT / _STALE_ROW / _BAD_LABEL).  NO synchronisation.
+    names: the class names (ASCII, at most 27 bytes each; None draws the class index); colors: (m, 3) RGB rows, class c has colors[c % m] (None: DEFAULT_COLORS);
+    line_width / font_scale: one int or one per image (None: the reference's defaults for the image's size, `render_defaults`); font_scale is the integer magnification
+    of the 6 x 11 cell; labels_on=False draws outlines only, conf=False leaves the score out.  The outline is PIL's `ImageDraw.rectangle(width=lw)` wherever
+    2 * lw <= min(box side) + 1; the text is Pillow's built-in bitmap font cell by cell and has no parity with the reference (it needs a downloaded Arial.ttf or cv2)."""
+    from .models.transform import YOLOTransform
+    lib = _lib.load(require_gpu=True)
+    images = [images[i] for i in range(len(images))]
+    n = len(images)
+    if not all(t.is_cuda for t in (boxes, scores, labels, counts)) or not all(im.is_cuda for im in images):
+        raise YmiError("draw_detections runs on an MI355X only (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(boxes.shape[:2]) or tuple(counts.shape) != (n,):
+        raise YmiError(f"draw_detections: expected the slab (n, K, 4) / (n, K) / (n, K) / (n,) for {n} images, got {tuple(boxes.shape)} {tuple(scores.shape)} {tuple(labels.shape)} {tuple(counts.shape)}")
+    k = int(boxes.shape[1])
+    dev = boxes.device
+    hwc = False
+    if n:
+        kinds = {(im.dtype, YOLOTransform.is_hwc(im)) for im in images}
+        if len(kinds) != 1:
+            raise YmiError("all images of a batch must share one dtype and layout")
+        hwc = YOLOTransform.is_hwc(images[0])
+        for im in images:
+            if im.dim() != 3 or (im.shape[0] != 3 and not hwc):
+                raise ValueError(f"images are expected to be (3, H, W) tensors (or (H, W, 3) uint8), got {tuple(im.shape)}")
+        if inplace:
+            if not all(im.is_contiguous() for im in images):
+                raise YmiError("draw_detections: inplace=True needs contiguous images")
+        else:
+            images = [im.clone(memory_format=torch.contiguous_format) for im in images]
+    sizes = [YOLOTransform.image_hw(im) for im in images]
+
+    def per_image(value, which):
+        if value is None:
+            return [render_defaults(int(h), int(w))[which] for h, w in sizes]
+        return [int(v) for v in value] if isinstance(value, (list, tuple)) else [int(value)] * n
+
+    lws, fss = per_image(line_width, 0), per_image(font_scale, 1)
+    if len(lws) != n or len(fss) != n:
+        raise ValueError("draw_detections: line_width / font_scale are one value or one per image")
+    d = _lib.RenderDesc()
+    ptrs = (C.c_void_p * max(n, 1))(*[im.data_ptr() for im in images])
+    hw = (C.c_int32 * max(2 * n, 1))(*[int(v) for s in sizes for v in s])
+    lw_a, fs_a = (C.c_int32 * max(n, 1))(*lws), (C.c_int32 * max(n, 1))(*fss)
+    b = boxes.detach().to(torch.float32).contiguous()
+    s = scores.detach().to(torch.float32).contiguous()
+    lab = labels.detach().to(torch.int64).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    table = _render_table("names", tuple(str(v) for v in names), dev) if names is not None else None
+    palette = _render_table("colors", tuple(int(v) for row in (DEFAULT_COLORS if colors is None else colors) for v in row), dev)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    d.imgs, d.hw = C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(hw, C.POINTER(C.c_int32))
+    d.lw, d.fs = C.cast(lw_a, C.POINTER(C.c_int32)), C.cast(fs_a, C.POINTER(C.c_int32))
+    d.boxes, d.scores, d.labels, d.counts, d.status = b.data_ptr(), s.data_ptr(), lab.data_ptr(), c.data_ptr(), status.data_ptr()
+    d.names, d.colors, d.m = (table.data_ptr() if table is not None else None), palette.data_ptr(), int(palette.shape[0])
+    for i in range(3):
+        d.txt_color[i] = int(txt_color[i])
+    d.num_classes = int(table.shape[0]) if table is not None else 2 ** 31 - 1
+    d.in_dtype = _lib.YMI_U8_HWC if hwc else (_lib.dtype_code(images[0].dtype) if n else _lib.YMI_F32)
+    d.draw_labels, d.draw_conf, d.n, d.k = int(bool(labels_on)), int(bool(conf)), n, k
+    check(lib.ymi_render(C.byref(d), _lib.stream_ptr()), "ymi_render")
+    return images, status
+
+
 def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence[int]) -> List[Dict[str, Tensor]]:
     """Fixed (N,K,..) slab -> the reference's List[Dict] with keys in its order (box_head.py:427)."""
     out = []
