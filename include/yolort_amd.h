@@ -72,6 +72,48 @@ int ymi_letterbox(const void* const* imgs, const int32_t* geom, int n, int in_dt
                   int wb, int c_out, int out_dtype, float fill, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * NV12 ingest: video frames as decoders deliver them -- a full-resolution Y plane plus one half-resolution plane of interleaved Cb/Cr pairs, each with its
+ * own row pitch -- letterboxed in ONE launch (YCbCr -> RGB fused into the staging of the tiled letterbox), or converted to interleaved RGB8.
+ * The conversion contract (integer arithmetic: exactly reproducible):
+ *   Chroma     nearest neighbour: luma pixel (y, x) uses the pair at chroma row y >> 1, byte offset x & ~1 (Cb first, then Cr).
+ *   Parameters matrix YMI_NV12_BT601 (Kr 0.299, Kb 0.114) | YMI_NV12_BT709 (Kr 0.2126, Kb 0.0722); range YMI_NV12_LIMITED (Y' = (Y - 16) * 255/219,
+ *              C' = (C - 128) * 255/224) | YMI_NV12_FULL (Y' = Y, C' = C - 128).
+ *   Real form  R = Y' + 2(1-Kr) Cr',  B = Y' + 2(1-Kb) Cb',  G = Y' - 2Kb(1-Kb)/Kg Cb' - 2Kr(1-Kr)/Kg Cr',  Kg = 1 - Kr - Kb.
+ *   Integers   each coefficient (range scale folded in) rounded to the nearest multiple of 2^-14: {cy, crv, cgu, cgv, cbu} =
+ *                BT.601 limited {19077, 26149, -6419, -13320, 33050}      BT.601 full {16384, 22970, -5638, -11700, 29032}
+ *                BT.709 limited {19077, 29372, -3494,  -8731, 34610}      BT.709 full {16384, 25802, -3069,  -7670, 30402}
+ *   Channel    R = clamp((cy (Y - yoff) + crv (Cr - 128) + 8192) >> 14), G = clamp((cy (Y - yoff) + cgu (Cb - 128) + cgv (Cr - 128) + 8192) >> 14),
+ *              B = clamp((cy (Y - yoff) + cbu (Cb - 128) + 8192) >> 14): int32 products and sums (largest magnitude about 9e6), an ARITHMETIC shift,
+ *              clamp to 0..255; yoff = 16 (limited) or 0 (full).
+ *   Error      within 0.5 + 495 * 2^-15 codes of the clamped real-valued formula (operand magnitudes 239 + 128 + 128, coefficient error <= 2^-15 each).
+ * ymi_letterbox_nv12: the canvas is ymi_letterbox(YMI_U8_HWC) of that RGB8 image BIT FOR BIT -- float(byte) / 255.0f per tap, the nested unfused lerp, one
+ * rounding to out_dtype; fill, the zero channels 3..c_out-1 and the geometry rows are ymi_letterbox's.  Kernels (csrc/preproc_nv12.hip):
+ * letterbox_nv12_tile_kernel (c_out 4) and the per-pixel letterbox_nv12_kernel (any c_out; also when no tile fits 64 KiB of LDS); the knobs
+ * YOLORT_AMD_LETTERBOX = pixel | 1 | 2 | 4 and YOLORT_AMD_LB_CG select them as for ymi_letterbox.  More than 64 frames go as several launches inside the call.
+ * YMI_EINVAL (nothing is launched): an odd h_in / w_in or a side below 2, a pitch that is odd or below w_in, an odd uv pointer, a bad matrix / range /
+ * out_dtype, c_out < 3, a frame that does not fit the canvas.  Nothing outside out's n * hb * wb pixels is written; nothing outside [0, w) of a source row is
+ * read except the aligned 16-byte chunk that holds a needed byte.  No allocation, no synchronisation: ordered on `stream`, may be captured.
+ * ymi_nv12_to_rgb: one frame -> rgb (h, w, 3) interleaved uint8, contiguous (nv12_to_rgb_kernel: 4 pixels = 12 bytes per thread); same refusals.
+ * ABI stays 6: one new struct, two new functions.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_NV12_BT601 0
+#define YMI_NV12_BT709 1
+#define YMI_NV12_LIMITED 0
+#define YMI_NV12_FULL 1
+typedef struct ymi_nv12_desc {
+    const void* const* y;  /* host array of n device pointers: Y plane of frame i */
+    const void* const* uv; /* host array of n device pointers: CbCr plane (2-byte aligned) */
+    const int32_t* pitch;  /* n x {pitch_y, pitch_uv} in bytes, each even and >= w_in */
+    const int32_t* geom;   /* n x 6, as ymi_letterbox */
+    int n, matrix, range;
+    void* out;
+    int hb, wb, c_out, out_dtype;
+    float fill;
+} ymi_nv12_desc;
+int ymi_letterbox_nv12(const ymi_nv12_desc* d, void* stream);
+int ymi_nv12_to_rgb(const void* y, const void* uv, int pitch_y, int pitch_uv, int h, int w, int matrix, int range, void* rgb, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * View canvas of augmented inference (test-time augmentation): a scaled, optionally left-right mirrored copy of the
  * letterboxed NHWC4 canvas.  Replaces yolort/v5/utils/torch_utils.py:288-300 (scale_img: F.interpolate bilinear,
  * align_corners=False, then F.pad with 0.447) and the x.flip(3) of yolort/v5/models/yolo.py:158, in one launch.

@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.environ.get("YOLORT_AMD_BUILD_OUT") or os.path.join(LIBDIR, "libyolort_amd.so")   # override: tuning builds only
-SOURCES = ["api.cpp", "conv_igemm.hip", "conv3x3_halo.hip", "conv_halo8.hip", "conv_igemm8.hip", "conv1x1_stream.hip", "conv3x3_c32.hip", "conv3x3_res.hip", "conv3x3_rw.hip", "conv3x3_rw2.hip", "conv3x3_rs.hip", "c3_fused32.hip", "c3_tile.hip", "stem_body1_fused.hip", "conv_stem.hip", "conv_f32.hip", "conv_f32_pipe.hip", "preproc_pool.hip", "postprocess.hip"]
+SOURCES = ["api.cpp", "conv_igemm.hip", "conv3x3_halo.hip", "conv_halo8.hip", "conv_igemm8.hip", "conv1x1_stream.hip", "conv3x3_c32.hip", "conv3x3_res.hip", "conv3x3_rw.hip", "conv3x3_rw2.hip", "conv3x3_rs.hip", "c3_fused32.hip", "c3_tile.hip", "stem_body1_fused.hip", "conv_stem.hip", "conv_f32.hip", "conv_f32_pipe.hip", "preproc_pool.hip", "preproc_nv12.hip", "postprocess.hip"]
 # the conv tile x dtype space and the fused heads are instantiated in their own translation units (parallel build)
 INST_SOURCES = sorted(f for f in os.listdir(CSRC) if (f.startswith("conv_inst_") or f.startswith("head_inst_")) and f.endswith(".hip"))
 MONOLITHIC = "-DYMI_STAMPS" in os.environ.get("YOLORT_AMD_BUILD_FLAGS", "")   # the timeline instrumentation keeps one device symbol: single TU
@@ -23,6 +23,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 FLAGS += os.environ.get("YOLORT_AMD_BUILD_FLAGS", "").split()
 if MONOLITHIC:
     FLAGS.append("-DYMI_MONOLITHIC")   # e.g. -DYMI_STAMPS for tools/stamp_conv.py
+# per-source flags: new translation units are compiled without the packed-fp32 instructions (v_pk_{add,mul,fma}_f32)
+SOURCE_FLAGS = {"preproc_nv12.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -37,6 +39,7 @@ def _digest() -> str:
     for f in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS:
         h.update(open(f, "rb").read())
     h.update(" ".join(FLAGS).encode())
+    h.update(repr(sorted(SOURCE_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -58,11 +61,12 @@ def build(force: bool = False, verbose: bool = True) -> str:
     def compile_one(src: str) -> str:
         obj = os.path.join(LIBDIR, os.path.splitext(src)[0] + (".dbg.o" if os.environ.get("YOLORT_AMD_BUILD_OUT") else ".o"))
         # incremental: an object is reused when its own source, every header and the flags are unchanged
-        odig = hashlib.sha256(open(os.path.join(CSRC, src), "rb").read() + hdr_digest.encode()).hexdigest()
+        extra = SOURCE_FLAGS.get(src, [])
+        odig = hashlib.sha256(open(os.path.join(CSRC, src), "rb").read() + hdr_digest.encode() + " ".join(extra).encode()).hexdigest()
         ostamp = obj + ".stamp"
         if not force and os.path.exists(obj) and os.path.exists(ostamp) and open(ostamp).read().strip() == odig:
             return obj
-        cmd = [hipcc, *FLAGS, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, *FLAGS, *extra, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stderr[-4000:]}")

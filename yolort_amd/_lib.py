@@ -136,6 +136,22 @@ class CropDesc(C.Structure):
     ]
 
 
+NV12_MATRIX = {"bt601": 0, "bt709": 1}        # YMI_NV12_BT601 / YMI_NV12_BT709
+NV12_LIMITED, NV12_FULL = 0, 1                 # YMI_NV12_LIMITED / YMI_NV12_FULL
+# {cy, crv, cgu, cgv, cbu} in units of 2^-14 per (matrix, full_range): the integers of the conversion contract (include/yolort_amd.h)
+NV12_COEF = {("bt601", False): (19077, 26149, -6419, -13320, 33050), ("bt601", True): (16384, 22970, -5638, -11700, 29032),
+             ("bt709", False): (19077, 29372, -3494, -8731, 34610), ("bt709", True): (16384, 25802, -3069, -7670, 30402)}
+
+
+class Nv12Desc(C.Structure):
+    """ymi_nv12_desc: the frames (host arrays of device pointers, pitches and geometry rows), the conversion and the canvas of one ymi_letterbox_nv12 call"""
+    _fields_ = [
+        ("y", C.POINTER(C.c_void_p)), ("uv", C.POINTER(C.c_void_p)), ("pitch", C.POINTER(C.c_int32)), ("geom", C.POINTER(C.c_int32)),
+        ("n", C.c_int), ("matrix", C.c_int), ("range", C.c_int), ("out", C.c_void_p),
+        ("hb", C.c_int), ("wb", C.c_int), ("c_out", C.c_int), ("out_dtype", C.c_int), ("fill", C.c_float),
+    ]
+
+
 RENDER_MAX_K, RENDER_NAME_STRIDE = 1024, 28   # YMI_RENDER_MAX_K, YMI_RENDER_NAME_STRIDE
 RENDER_STATUS_BAD_COUNT, RENDER_STATUS_STALE_ROW, RENDER_STATUS_BAD_LABEL = 1, 2, 4   # YMI_RENDER_STATUS_*: bits of the status word
 
@@ -186,6 +202,8 @@ _SIGS = {
     "ymi_last_error": (C.c_char_p, []),
     "ymi_device_count": (C.c_int, []),
     "ymi_letterbox": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "ymi_letterbox_nv12": (C.c_int, [C.POINTER(Nv12Desc), C.c_void_p]),
+    "ymi_nv12_to_rgb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ymi_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ymi_nhwc_to_nchw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "ymi_conv2d": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p]),

@@ -90,8 +90,19 @@ class YOLOv5(nn.Module):
                 if not im.is_cuda:
                     raise YmiError("yolort_amd runs on an MI355X only: move the model and inputs to 'cuda' (there is no CPU fallback)")
             original = [self.transform.image_hw(im) for im in images]   # (3, H, W) planar, or (H, W, 3) interleaved uint8
-        # host geometry (resize / pad / rescale rows) depends on the list of image sizes only: memoised, a serving loop sees
-        # the same few size lists again and again
+        (hb, wb), sizes, pads, rows_cached, identity = self._geometry_cached(original, canvas)
+        model = self.model
+        if not isinstance(model, YOLO):
+            raise YmiError("YOLOv5.model must be a yolort_amd YOLO")
+        dev = images[0].device
+        if dev.index == torch.cuda.current_device():
+            return self._enqueue(model, images, (hb, wb), sizes, pads, rows_cached, identity, original, scan)
+        with torch.cuda.device(dev):   # plans, streams and launches belong to the images' device
+            return self._enqueue(model, images, (hb, wb), sizes, pads, rows_cached, identity, original, scan)
+
+    def _geometry_cached(self, original, canvas):
+        """host geometry (resize / pad / rescale rows) depends on the list of image sizes only: memoised, a serving loop sees the same few size lists again and again
+        -> ((hb, wb), sizes, pads, rescale rows, identity)"""
         gkey = (tuple(original), self.transform.min_size, self.transform.max_size, self.transform.size_divisible, self.transform.fixed_shape,
                 None if canvas is None else (int(canvas[0]), int(canvas[1])))
         geo = self._geo_cache.get(gkey) if hasattr(self, "_geo_cache") else None
@@ -104,27 +115,54 @@ class YOLOv5(nn.Module):
             if len(self._geo_cache) > 256:
                 self._geo_cache.clear()
             self._geo_cache[gkey] = geo
-        (hb, wb), sizes, pads, rows_cached, identity = geo
+        return geo
+
+    def forward_nv12(self, frames, *, matrix: str = "bt601", full_range: bool = False, canvas: Optional[Tuple[int, int]] = None):
+        """Detection on NV12 video frames as decoders deliver them (ops.nv12_planes: the packed (3h/2, w) uint8 buffer, or a pair (y, uv) of pitched planes): forward()'s
+        geometry, plan, graph, side stream and rescale path, with the canvas filled by ymi_letterbox_nv12 -- the YCbCr -> RGB conversion (`matrix` "bt601" / "bt709",
+        limited or full range) runs inside the letterbox kernel.  Returns exactly forward([ops.nv12_to_rgb(f) for f in frames]): boxes in frame pixel coordinates."""
+        return self.forward_nv12_async(frames, matrix=matrix, full_range=full_range, canvas=canvas).result()
+
+    def forward_nv12_async(self, frames, *, matrix: str = "bt601", full_range: bool = False, canvas: Optional[Tuple[int, int]] = None):
+        """forward_async for NV12 frames (see forward_nv12)"""
+        from .. import ops
+        if self.training:
+            raise NotImplementedError("yolort_amd implements the inference path only; call .eval() (training is out of scope)")
+        planes = [ops.nv12_planes(frames[i]) for i in range(len(frames))]
+        if not planes:
+            raise ValueError("forward_nv12: no frames")
+        nv12 = (planes,) + ops._nv12_params(matrix, full_range)
+        dev = planes[0][0].device
+        if not all(p[0].is_cuda and p[0].device == dev for p in planes):
+            raise YmiError("yolort_amd runs on an MI355X only: move the model and inputs to one 'cuda' device (there is no CPU fallback)")
+        original = [(p[2], p[3]) for p in planes]
+        (hb, wb), sizes, pads, rows_cached, identity = self._geometry_cached(original, canvas)
         model = self.model
         if not isinstance(model, YOLO):
             raise YmiError("YOLOv5.model must be a yolort_amd YOLO")
-        dev = images[0].device
-        if dev.index == torch.cuda.current_device():
-            return self._enqueue(model, images, (hb, wb), sizes, pads, rows_cached, identity, original, scan)
-        with torch.cuda.device(dev):   # plans, streams and launches belong to the images' device
-            return self._enqueue(model, images, (hb, wb), sizes, pads, rows_cached, identity, original, scan)
+        images = [t for p in planes for t in p[:2]]
+        with torch.cuda.device(dev):   # plans, streams and launches belong to the frames' device
+            return self._enqueue(model, images, (hb, wb), sizes, pads, rows_cached, identity, original, None, nv12)
 
-    def _enqueue(self, model: YOLO, images, canvas, sizes, pads, rows_cached, identity, original, scan=None):
+    def _enqueue(self, model: YOLO, images, canvas, sizes, pads, rows_cached, identity, original, scan=None, nv12=None):
+        """`nv12` = (planes, matrix, range): the canvas is filled from NV12 frames (`images` then lists their plane tensors), never by the planar-stem shortcut"""
         hb, wb = canvas
-        e = model._acquire(len(images), hb, wb, images[0].device)
+        e = model._acquire(len(original), hb, wb, images[0].device)
         main = e.main_stream   # every launch below names its stream: no stream context is entered on the default path
         # fixed-size stream: every image already is the canvas (resize = identity, no padding) in the compute dtype ->
         # the stem reads the planar images itself, the letterbox pass and its NHWC4 copy are skipped (bit-identical)
         # (not under augmented inference: the canvas itself is the source of the smaller views, so it has to be filled)
-        planar = model.stem_from_planar and not getattr(model, "augment", False) and identity and e.plan.stem_planar_ok(images, (hb, wb), scan)
+        planar = nv12 is None and model.stem_from_planar and not getattr(model, "augment", False) and identity and e.plan.stem_planar_ok(images, (hb, wb), scan)
         ev0 = None
         first_op = 0
         ptrs = None
+        if nv12 is None:
+            def fill_canvas():
+                self.transform.letterbox_into(images, e.x, sizes, pads, stream=main, ptrs=ptrs, uniform_kind=scan is not None)
+        else:
+            def fill_canvas():
+                from .. import ops
+                ops.launch_letterbox_nv12(nv12[0], sizes, pads, e.x.ptr, e.x.h, e.x.w, e.x.c, e.x.dtype, nv12[1], nv12[2], self.transform.fill_color, stream=main)
         if scan is not None:   # allocated on the caller's stream, read on the instance's
             hipmodule._SIG_EXT.record_stream(images, main.stream_id, main.device_index, main.device_type)
             ptrs = scan[7] if scan[5] else None
@@ -139,12 +177,12 @@ class YOLOv5(nn.Module):
         elif model.bracket is not None:
             l0, l1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             l0.record(main)
-            self.transform.letterbox_into(images, e.x, sizes, pads, stream=main, ptrs=ptrs, uniform_kind=scan is not None)
+            fill_canvas()
             l1.record(main)
             model.bracket["pre"][0].append(l0)
             model.bracket["pre"][1].append(l1)
         else:
-            self.transform.letterbox_into(images, e.x, sizes, pads, stream=main, ptrs=ptrs, uniform_kind=scan is not None)
+            fill_canvas()
         rows = rows_cached
         if e.post is None:  # custom post_process hook (torch modules: they run in the instance's stream context); rescale afterwards like the reference (yolov5.py:181)
             with torch.cuda.stream(main):

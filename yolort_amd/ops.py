@@ -127,6 +127,91 @@ def match_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tens
     return tp, ig, rank, n_gt
 
 
+def nv12_planes(frame):
+    """A video frame in NV12 -> (y, uv, h, w): the Y plane (h, w) and the CbCr plane (h / 2, w) as 2-D uint8 views with stride(1) == 1 (the row stride is the pitch).
+    `frame` is the packed buffer -- a contiguous 2-D uint8 tensor (3h / 2, w): Y rows, then chroma rows -- or a pair (y, uv) of such views, which is how pitched decoder
+    surfaces arrive.  ValueError for anything else; sides are even and >= 2, pitches even, the chroma plane 2-byte aligned."""
+    if isinstance(frame, Tensor):
+        if frame.dim() != 2 or frame.dtype != torch.uint8 or not frame.is_contiguous() or frame.shape[0] % 3 != 0:
+            raise ValueError(f"an NV12 frame is a contiguous 2-D uint8 tensor (3h/2, w) or a pair (y, uv), got {frame.dtype} {tuple(frame.shape)}")
+        h = frame.shape[0] // 3 * 2
+        y, uv = frame[:h], frame[h:]
+    else:
+        if len(frame) != 2 or not all(isinstance(t, Tensor) and t.dim() == 2 and t.dtype == torch.uint8 for t in frame):
+            raise ValueError("an NV12 frame is a contiguous 2-D uint8 tensor (3h/2, w) or a pair (y, uv) of 2-D uint8 tensors")
+        y, uv = frame
+    h, w = int(y.shape[0]), int(y.shape[1])
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f"NV12 frames have even sides >= 2, got {h} x {w}")
+    if tuple(uv.shape) != (h // 2, w):
+        raise ValueError(f"the CbCr plane of a {h} x {w} frame is ({h // 2}, {w}) bytes, got {tuple(uv.shape)}")
+    for t, name in ((y, "Y"), (uv, "CbCr")):
+        if t.stride(1) != 1 or t.stride(0) < w or t.stride(0) % 2:
+            raise ValueError(f"the {name} plane needs stride(1) == 1 and an even row pitch >= the width, got strides {tuple(t.stride())}")
+    if uv.data_ptr() % 2:
+        raise ValueError("the CbCr plane must be 2-byte aligned")
+    if y.device != uv.device:
+        raise ValueError("the planes of a frame live on one device")
+    return y, uv, h, w
+
+
+def _nv12_params(matrix: str, full_range: bool):
+    if matrix not in _lib.NV12_MATRIX:
+        raise ValueError(f"matrix must be 'bt601' or 'bt709', got {matrix!r}")
+    return _lib.NV12_MATRIX[matrix], _lib.NV12_FULL if full_range else _lib.NV12_LIMITED
+
+
+def nv12_to_rgb(frame, *, matrix: str = "bt601", full_range: bool = False) -> Tensor:
+    """One NV12 frame (see nv12_planes) -> interleaved RGB (h, w, 3) uint8 on the MI355X (ymi_nv12_to_rgb): the integer conversion contract of include/yolort_amd.h
+    -- nearest chroma, BT.601 / BT.709, limited / full range, coefficients in 2^-14 units -- exactly reproducible.  The image `YOLOv5.forward`, ops.crop_detections and
+    ops.draw_detections take for video frames.  No CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    y, uv, h, w = nv12_planes(frame)
+    m, r = _nv12_params(matrix, full_range)
+    if not y.is_cuda:
+        raise YmiError("nv12_to_rgb runs on an MI355X only (no CPU fallback)")
+    rgb = torch.empty((h, w, 3), device=y.device, dtype=torch.uint8)
+    check(lib.ymi_nv12_to_rgb(y.data_ptr(), uv.data_ptr(), y.stride(0), uv.stride(0), h, w, m, r, rgb.data_ptr(), _lib.stream_ptr()), "ymi_nv12_to_rgb")
+    return rgb
+
+
+def launch_letterbox_nv12(planes, sizes, pads, out_ptr, hb: int, wb: int, c_out: int, out_dtype: torch.dtype, matrix: int, rng: int, fill: float, stream=None) -> None:
+    """one ymi_letterbox_nv12 call on `stream` for frames already taken apart by nv12_planes: planes = [(y, uv, h, w)], sizes = [(h_res, w_res)], pads = [(top, left)]"""
+    lib = _lib.load(require_gpu=True)
+    n = len(planes)
+    d = _lib.Nv12Desc()
+    ys = (C.c_void_p * max(n, 1))(*[p[0].data_ptr() for p in planes])
+    uvs = (C.c_void_p * max(n, 1))(*[p[1].data_ptr() for p in planes])
+    pitch = (C.c_int32 * max(2 * n, 1))(*[v for p in planes for v in (p[0].stride(0), p[1].stride(0))])
+    geom = (C.c_int32 * max(6 * n, 1))(*[v for p, s_, q in zip(planes, sizes, pads) for v in (p[2], p[3], s_[0], s_[1], q[0], q[1])])
+    d.y, d.uv = C.cast(ys, C.POINTER(C.c_void_p)), C.cast(uvs, C.POINTER(C.c_void_p))
+    d.pitch, d.geom = C.cast(pitch, C.POINTER(C.c_int32)), C.cast(geom, C.POINTER(C.c_int32))
+    d.n, d.matrix, d.range, d.out = n, matrix, rng, out_ptr
+    d.hb, d.wb, d.c_out, d.out_dtype, d.fill = hb, wb, c_out, _lib.dtype_code(out_dtype), float(fill)
+    check(lib.ymi_letterbox_nv12(C.byref(d), _lib.stream_ptr(stream)), "ymi_letterbox_nv12")
+
+
+def letterbox_nv12(frames, sizes, pads, canvas_hw, *, matrix: str = "bt601", full_range: bool = False, dtype: torch.dtype = torch.float16, c_out: int = 4,
+                   fill: float = 114 / 255) -> Tensor:
+    """NV12 frames (see nv12_planes) letterboxed onto one canvas in ONE launch per 64 frames, the colour conversion fused into the letterbox kernel
+    (ymi_letterbox_nv12) -> (n, hb, wb, c_out) of `dtype` (fp16 / bf16 / fp32): bit for bit the canvas ymi_letterbox writes for nv12_to_rgb's images.  sizes =
+    [(h_res, w_res)] and pads = [(top, left)] per frame, as YOLOTransform.geometry returns them; channels 3 and above are zero.  No CPU fallback."""
+    planes = [nv12_planes(f) for f in frames]
+    m, r = _nv12_params(matrix, full_range)
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"letterbox_nv12: dtype must be float16, bfloat16 or float32, got {dtype}")
+    if len(sizes) != len(planes) or len(pads) != len(planes):
+        raise ValueError(f"letterbox_nv12: {len(planes)} frames, {len(sizes)} sizes, {len(pads)} pads")
+    if not planes:
+        raise ValueError("letterbox_nv12: no frames")
+    if not all(p[0].is_cuda for p in planes):
+        raise YmiError("letterbox_nv12 runs on an MI355X only (no CPU fallback)")
+    hb, wb = int(canvas_hw[0]), int(canvas_hw[1])
+    out = torch.empty((len(planes), hb, wb, int(c_out)), device=planes[0][0].device, dtype=dtype)
+    launch_letterbox_nv12(planes, sizes, pads, out.data_ptr(), hb, wb, int(c_out), dtype, m, r, fill)
+    return out
+
+
 def crop_detections(images: Sequence[Tensor], boxes: Tensor, counts: Tensor, size, *, gain: float = 1.02, pad: float = 10, square: bool = False,
                     mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None, dtype: torch.dtype = torch.float16, capacity: Optional[int] = None):
     """Every detection of the slab cut out of its original image and resized to `size` = (out_h, out_w), on the MI355X in one launch per batch (ymi_crop_resize,
