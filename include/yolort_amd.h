@@ -253,6 +253,78 @@ typedef struct ymi_render_desc {
 } ymi_render_desc;
 int ymi_render(const ymi_render_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * NV12 drawing and cropping: the far end of the video path -- detections drawn straight into the Y and CbCr planes a hardware encoder takes, and cut out of the
+ * planes a decoder delivered, with no RGB copy of the frame in between.  Frames are given as in ymi_nv12_desc (y[], uv[], pitch[] = n x {pitch_y, pitch_uv}) plus
+ * hw[] = n x {h, w}; the frame rules are those of NV12 ingest: even sides >= 2, even pitches >= w, a 2-byte-aligned chroma plane.
+ * RGB -> YCbCr, the inverse of the ingest conversion in the same style (integer arithmetic: exactly reproducible); matrix and range are YMI_NV12_*:
+ *   Real form  Y' = Kr R + Kg G + Kb B,  Cb' = (B - Y') / (2 (1 - Kb)),  Cr' = (R - Y') / (2 (1 - Kr)),  Kg = 1 - Kr - Kb;  full range: Y = Y', C = C' + 128;
+ *              limited range: Y = Y' * 219/255 + 16, C = C' * 224/255 + 128.
+ *   Integers   each of the nine coefficients (range scale folded in) rounded to the nearest multiple of 2^-14: {cyr, cyg, cyb, cbr, cbg, cbb, crr, crg, crb} =
+ *                BT.601 limited {4207,  8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170}    BT.601 full {4899,  9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332}
+ *                BT.709 limited {2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536,  -660}    BT.709 full {3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441,  -751}
+ *   Channel    Y  = clamp(((cyr R + cyg G + cyb B + 8192) >> 14) + yoff),  Cb = clamp(((cbr R + cbg G + cbb B + 8192) >> 14) + 128),
+ *              Cr = clamp(((crr R + crg G + crb B + 8192) >> 14) + 128): int32 products and sums, ARITHMETIC shifts, clamp to 0..255; yoff = 16 (limited) or 0 (full).
+ *   Error      within 0.5 + 3 * 255 * 2^-15 codes of the real-valued formula before the clamp (three coefficients, each off by at most 2^-15, times values <= 255;
+ *              0.5 for the rounding shift).
+ *   The conversion is applied once per colour -- the box colour of a listed detection, the text colour -- never per pixel.
+ * ymi_render_nv12: ymi_render's DRAWING RULE per LUMA pixel, unchanged: which detection decides a pixel, and whether as outline, label background or glyph (the
+ * kernels share that code, csrc/draw_common.hpp).  names, colors, lw, fs, draw_labels, draw_conf, txt_color, counts and the status bits are ymi_render's, and so are
+ * k <= YMI_RENDER_MAX_K and the 64 frames per launch (more go as several launches inside the call).
+ *   Luma     a decided pixel gets the Y of its colour.
+ *   Chroma   the pair at chroma row cy, byte offset 2 cx belongs to luma pixels (2 cy .. 2 cy + 1, 2 cx .. 2 cx + 1).  It is written iff at least one of the four is
+ *            decided, and takes (Cb, Cr) of the colour that decided the FIRST decided one in raster order (top-left, top-right, bottom-left, bottom-right).
+ *   Writes   nothing else: no undecided pixel or pair, no pitch padding, nothing of a tile no detection reaches (such a tile is not read either).
+ * render_nv12_kernel (csrc/preproc_nv12.hip): a workgroup of 256 threads owns a 64 x 16 luma tile = 32 x 8 chroma pairs; it builds render_kernel's list (each entry
+ * with its converted colour), decides four adjacent luma pixels per thread, leaves their 16-bit codes in an LDS tile and stores Y (one 32-bit store where all four
+ * are decided and the address is aligned, byte stores else); after a barrier each thread resolves one pair from its 2 x 2 codes and stores it as 16 bits.  No atomics on pixels.
+ * ymi_crop_resize_nv12: ymi_crop_resize with the images given as NV12 frames; crops, index and total are BIT FOR BIT those of ymi_crop_resize(YMI_U8_HWC) on
+ * ymi_nv12_to_rgb's images (crop_resize_nv12_kernel is crop_resize_kernel's body with the four taps fetched from the planes and converted by the ingest contract).
+ * YMI_EINVAL (nothing is launched): what ymi_render / ymi_crop_resize refuse, a frame that breaks the rules above, a bad matrix / range.  No allocation, no
+ * synchronisation: ordered on `stream`, may be captured.  Not offered: a stand-alone RGB -> NV12 frame conversion, bilinear or averaged chroma, P010 / I420,
+ * anti-aliasing.  ABI stays 6: two new structs, two new functions.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct ymi_render_nv12_desc {
+    void* const* y;       /* host array of n device pointers: Y plane of frame i, WRITTEN in place */
+    void* const* uv;      /* host array of n device pointers: CbCr plane (2-byte aligned), WRITTEN in place */
+    const int32_t* pitch; /* n x {pitch_y, pitch_uv} in bytes */
+    const int32_t* hw;    /* n x {h, w} */
+    const int32_t* lw;
+    const int32_t* fs;
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const uint8_t* names;
+    const uint8_t* colors;
+    int32_t* status;
+    int32_t m;
+    int32_t txt_color[3];
+    int32_t num_classes, matrix, range;
+    int32_t draw_labels, draw_conf;
+    int32_t n, k;
+    int32_t reserved;
+} ymi_render_nv12_desc;
+int ymi_render_nv12(const ymi_render_nv12_desc* d, void* stream);
+typedef struct ymi_crop_nv12_desc {
+    const void* const* y;
+    const void* const* uv;
+    const int32_t* pitch;
+    const int32_t* hw;
+    const float* boxes;
+    const int32_t* counts;
+    void* crops;
+    int32_t* index;
+    int32_t* total;
+    float mean[3], std[3];
+    float gain, pad;
+    int32_t n, k, cap;
+    int32_t out_h, out_w;
+    int32_t matrix, range, out_dtype;
+    int32_t square, normalize;
+} ymi_crop_nv12_desc;
+int ymi_crop_resize_nv12(const ymi_crop_nv12_desc* d, void* stream);
+
 /* NCHW (n,c,h,w) -> NHWC view and back (module-level API edges; not on the fused path). */
 int ymi_nchw_to_nhwc(const void* x, int n, int c, int h, int w, int in_dtype, void* y, int y_cstride,
                      int c_pad, int out_dtype, void* stream);

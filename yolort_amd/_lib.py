@@ -167,6 +167,33 @@ class RenderDesc(C.Structure):
     ]
 
 
+# {cyr, cyg, cyb, cbr, cbg, cbb, crr, crg, crb} in units of 2^-14 per (matrix, full_range): the integers of the RGB -> YCbCr contract (include/yolort_amd.h)
+YCC_COEF = {("bt601", False): (4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170), ("bt601", True): (4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332),
+            ("bt709", False): (2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660), ("bt709", True): (3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751)}
+
+
+class RenderNv12Desc(C.Structure):
+    """ymi_render_nv12_desc: ymi_render_desc with the images given as NV12 planes (host arrays of device pointers, pitches and sizes) plus the conversion"""
+    _fields_ = [
+        ("y", C.POINTER(C.c_void_p)), ("uv", C.POINTER(C.c_void_p)), ("pitch", C.POINTER(C.c_int32)), ("hw", C.POINTER(C.c_int32)), ("lw", C.POINTER(C.c_int32)),
+        ("fs", C.POINTER(C.c_int32)),
+        ("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p), ("names", C.c_void_p), ("colors", C.c_void_p), ("status", C.c_void_p),
+        ("m", C.c_int32), ("txt_color", C.c_int32 * 3), ("num_classes", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("draw_labels", C.c_int32),
+        ("draw_conf", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class CropNv12Desc(C.Structure):
+    """ymi_crop_nv12_desc: ymi_crop_desc with the images given as NV12 planes plus the conversion"""
+    _fields_ = [
+        ("y", C.POINTER(C.c_void_p)), ("uv", C.POINTER(C.c_void_p)), ("pitch", C.POINTER(C.c_int32)), ("hw", C.POINTER(C.c_int32)), ("boxes", C.c_void_p),
+        ("counts", C.c_void_p), ("crops", C.c_void_p), ("index", C.c_void_p), ("total", C.c_void_p),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3), ("gain", C.c_float), ("pad", C.c_float),
+        ("n", C.c_int32), ("k", C.c_int32), ("cap", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+        ("matrix", C.c_int32), ("range", C.c_int32), ("out_dtype", C.c_int32), ("square", C.c_int32), ("normalize", C.c_int32),
+    ]
+
+
 VIEW_PAD = 0.447  # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
 TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
 
@@ -243,6 +270,8 @@ _SIGS = {
     "ymi_eval_match": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p]),
     "ymi_crop_resize": (C.c_int, [C.POINTER(CropDesc), C.c_void_p]),
     "ymi_render": (C.c_int, [C.POINTER(RenderDesc), C.c_void_p]),
+    "ymi_render_nv12": (C.c_int, [C.POINTER(RenderNv12Desc), C.c_void_p]),
+    "ymi_crop_resize_nv12": (C.c_int, [C.POINTER(CropNv12Desc), C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "draw_common.hpp"
 
 namespace ymi {
 
@@ -348,6 +349,168 @@ static size_t nv12_tile_lds(const Nv12Args& a, int th, int tw, size_t cap = 64 *
     return need <= cap ? need : 0;   // the largest dynamic LDS request that needs no opt-in
 }
 
+// ---------------------------------------------------------------------------------------------
+// The far end of the video path (include/yolort_amd.h, "NV12 drawing and cropping"): detections drawn straight into the Y and CbCr planes, and cut out of them.
+// RGB -> YCbCr is the integer contract of the header -- nine coefficients in units of 2^-14 per [matrix][range], one rounding shift, offset, clamp -- and is applied
+// ONCE PER LIST ENTRY (the box colour of a listed detection) and once to the text colour, never per pixel.
+// ---------------------------------------------------------------------------------------------
+// {cyr, cyg, cyb, cbr, cbg, cbb, crr, crg, crb} per [matrix][range]: round-to-nearest multiples of 2^-14 of the real coefficients (listed in the header)
+static const int YCC_COEF[2][2][9] = {{{4207, 8260, 1604, -2428, -4768, 7196, 7196, -6026, -1170}, {4899, 9617, 1868, -2765, -5427, 8192, 8192, -6860, -1332}},
+                                      {{2991, 10064, 1016, -1649, -5547, 7196, 7196, -6536, -660}, {3483, 11718, 1183, -1877, -6315, 8192, 8192, -7441, -751}}};
+struct YccCoef {
+    int yoff, c[9];
+};
+// r | g << 8 | b << 16  ->  Y | Cb << 8 | Cr << 16
+__device__ __forceinline__ uint32_t rgb_to_ycc(uint32_t rgb, const YccCoef& k) {
+    const int r = (int)(rgb & 255u), g = (int)((rgb >> 8) & 255u), b = (int)((rgb >> 16) & 255u);
+    int y = ((k.c[0] * r + k.c[1] * g + k.c[2] * b + 8192) >> 14) + k.yoff;   // arithmetic shifts
+    int cb = ((k.c[3] * r + k.c[4] * g + k.c[5] * b + 8192) >> 14) + 128;
+    int cr = ((k.c[6] * r + k.c[7] * g + k.c[8] * b + 8192) >> 14) + 128;
+    y = min(max(y, 0), 255);
+    cb = min(max(cb, 0), 255);
+    cr = min(max(cr, 0), 255);
+    return (uint32_t)y | ((uint32_t)cb << 8) | ((uint32_t)cr << 16);
+}
+
+// ---------------------------------------------------------------------------------------------
+// render_nv12_kernel: ymi_render's rule per LUMA pixel (render_list and render_decide of csrc/draw_common.hpp: the code render_kernel runs), written into NV12 planes.
+// A workgroup of 256 threads owns a 64 x 16 luma tile = 32 x 8 chroma pairs, one per thread; frame sides are even, so a tile never splits a pair.
+//   Phase 1  the tile's list in slot order (render_list); the entry stored at position i also gets ycc[i] = the {Y, Cb, Cr} of its box colour.  An empty list: return,
+//            nothing of the frame is read or written.
+//   Phase 2  a thread owns four adjacent luma pixels of a row, decides them, writes their four 16-bit codes -- 0: untouched, else (list position + 1) << 1 | glyph --
+//            to the 64 x 16 code tile in LDS as ONE 8-byte store, and stores Y: one 32-bit store when all four are decided and the address is 4-byte aligned (it
+//            depends on the plane's base, the pitch and the row), byte stores of the decided ones otherwise.
+//   Barrier.
+//   Phase 3  a thread reads the 2 x 2 codes of its pair (two 32-bit LDS reads), takes the FIRST non-zero one in raster order, looks (Cb, Cr) up in ycc[] (or takes the
+//            text colour's) and stores the pair as ONE 16-bit store.  A pair none of whose four pixels is decided is not written.
+// No atomics on pixels, no races (a byte has one owner per phase), no allocation.  LDS: 36 B per slab slot + 2 064 B (k = 300: 12 864 B, k = 1024: 38 928 B).
+// ---------------------------------------------------------------------------------------------
+struct RenderNv12Args {
+    unsigned char* y[NV12_MAX];   // frames img_base .. img_base + img_n - 1
+    unsigned char* uv[NV12_MAX];
+    int pitch[NV12_MAX][2];       // bytes per Y row, per CbCr row
+    int hw[NV12_MAX][2];
+    int lwfs[NV12_MAX][2];        // outline width, font scale
+    int tile_end[NV12_MAX];       // inclusive prefix of the frames' tile counts
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const uint8_t* names;
+    const uint8_t* colors;
+    int32_t* status;
+    int img_base, img_n, k, m, num_classes, draw_labels, draw_conf;
+    uint32_t txt;                 // r | g << 8 | b << 16
+    YccCoef c;
+};
+static_assert(sizeof(RenderNv12Args) < 4096, "the by-value descriptor table must stay under 4 KiB of kernarg");
+constexpr size_t RD_CODES_BYTES = (size_t)RD_TW * RD_TH * sizeof(uint16_t);
+static size_t render_nv12_lds(int k) { return (size_t)k * (sizeof(RenderEntry) + sizeof(uint32_t)) + RD_CODES_BYTES + 4 * sizeof(int); }
+
+__global__ __launch_bounds__(256) void render_nv12_kernel(const RenderNv12Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char nv12_sm[];
+    RenderEntry* list = reinterpret_cast<RenderEntry*>(nv12_sm);                                           // k entries
+    uint16_t* codes = reinterpret_cast<uint16_t*>(nv12_sm + (size_t)a.k * sizeof(RenderEntry));            // RD_TH rows of RD_TW codes (16-byte aligned)
+    int* wcnt = reinterpret_cast<int*>(nv12_sm + (size_t)a.k * sizeof(RenderEntry) + RD_CODES_BYTES);      // the four wave totals of a pass
+    uint32_t* ycc = reinterpret_cast<uint32_t*>(wcnt + 4);                                                 // k words: Y | Cb << 8 | Cr << 16 of entry i's box colour
+    const int tid = (int)threadIdx.x;
+    int li = 0;
+    for (int i = 0; i < a.img_n - 1; ++i) li += (int)blockIdx.x >= a.tile_end[i] ? 1 : 0;   // block-uniform
+    const int tile = (int)blockIdx.x - (li ? a.tile_end[li - 1] : 0);
+    const int H = a.hw[li][0], W = a.hw[li][1], lw = a.lwfs[li][0], fs = a.lwfs[li][1];
+    const int tiles_x = (W + RD_TW - 1) / RD_TW;
+    const int tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+    const int tx0 = txi * RD_TW, ty0 = tyi * RD_TH;
+    // ---- phase 1 ----
+    const int nlist = render_list(a, a.img_base + li, tile, tx0, ty0, fs, wcnt, [&](int off, const RenderEntry& e) {
+        list[off] = e;
+        ycc[off] = rgb_to_ycc(e.rgb, a.c);
+    });
+    if (nlist == 0) return;   // block-uniform: nothing meets this tile, the frame is neither read nor written
+    const uint32_t txt = rgb_to_ycc(a.txt, a.c);   // uniform: once per workgroup, in scalar registers
+    // ---- phase 2: four adjacent luma pixels per thread ----
+    {
+        const int yl = tid >> 4, xl = (tid & 15) * 4;
+        const int y = ty0 + yl, x = tx0 + xl;
+        uint32_t code[4] = {0u, 0u, 0u, 0u}, lum[4] = {0u, 0u, 0u, 0u};
+        unsigned found = 0;
+        if (y < H && x < W) {
+            const unsigned want = x + 3 < W ? 0xfu : ((1u << (W - x)) - 1u);
+            found = render_decide(list, nlist, x, y, want, lw, fs, a.names, [&](int p, int i, const RenderEntry&, bool glyph) {
+                code[p] = ((uint32_t)(i + 1) << 1) | (glyph ? 1u : 0u);
+                lum[p] = (glyph ? txt : ycc[i]) & 255u;
+            });
+        }
+        const u32x2 cw = {code[0] | (code[1] << 16), code[2] | (code[3] << 16)};
+        *reinterpret_cast<u32x2*>(codes + yl * RD_TW + xl) = cw;   // every thread, also outside the frame: phase 3 reads whole 2 x 2 blocks
+        if (found) {
+            unsigned char* o = a.y[li] + (int64_t)y * a.pitch[li][0] + x;
+            if (found == 0xfu && ((uintptr_t)o & 3) == 0) {
+                *reinterpret_cast<uint32_t*>(o) = lum[0] | (lum[1] << 8) | (lum[2] << 16) | (lum[3] << 24);
+            } else {
+#pragma unroll
+                for (int p = 0; p < 4; ++p)
+                    if ((found >> p) & 1u) o[p] = (unsigned char)lum[p];
+            }
+        }
+    }
+    __syncthreads();
+    // ---- phase 3: one chroma pair per thread ----
+    const int cyl = tid >> 5, cxl = tid & 31;
+    const int yy = ty0 + 2 * cyl, xx = tx0 + 2 * cxl;   // the pair's top-left luma pixel; the sides are even, so the other three exist with it
+    if (yy >= H || xx >= W) return;
+    const uint32_t top = *reinterpret_cast<const uint32_t*>(codes + (2 * cyl) * RD_TW + 2 * cxl);
+    const uint32_t bot = *reinterpret_cast<const uint32_t*>(codes + (2 * cyl + 1) * RD_TW + 2 * cxl);
+    const uint32_t c = (top & 0xffffu) ? (top & 0xffffu) : ((top >> 16) ? (top >> 16) : ((bot & 0xffffu) ? (bot & 0xffffu) : (bot >> 16)));
+    if (c == 0u) return;
+    const uint32_t v = (c & 1u) ? txt : ycc[(c >> 1) - 1u];
+    *reinterpret_cast<uint16_t*>(a.uv[li] + (int64_t)(yy >> 1) * a.pitch[li][1] + xx) = (uint16_t)(v >> 8);   // Cb, then Cr; 2-byte aligned: uv, the pitch and xx are even
+}
+
+// ---------------------------------------------------------------------------------------------
+// crop_resize_nv12_kernel: crop_resize_kernel's body (crop_resize_body, csrc/draw_common.hpp) with ONE difference, the source fetch: a tap is nv12_pixel -- the frame's
+// luma byte and its nearest chroma pair converted by the ingest contract -- read as float(byte) / 255.0f, exactly what crop_resize_kernel<YMI_U8_HWC> reads from
+// ymi_nv12_to_rgb's image.  Bit for bit ymi_crop_resize of that image, without the image.
+// ---------------------------------------------------------------------------------------------
+struct CropNv12Args {
+    const unsigned char* y[NV12_MAX];   // frames img_base .. img_base + img_n - 1
+    const unsigned char* uv[NV12_MAX];
+    int pitch[NV12_MAX][2];
+    int hw[NV12_MAX][2];
+    const float* boxes;
+    const int32_t* counts;
+    void* crops;
+    int32_t* index;
+    int32_t* total;
+    int n, img_base, img_n, k, cap, out_h, out_w, tiles, square, normalize;
+    float gain, pad, mean[3], std[3];
+    Nv12Coef c;
+};
+static_assert(sizeof(CropNv12Args) < 4096, "the by-value descriptor table must stay under 4 KiB of kernarg");
+struct CropSrcNv12 {
+    typedef uint32_t Pixel;   // RGBX8
+    const unsigned char *yp, *up;
+    int py, puv;
+    const Nv12Coef& k;
+    __device__ __forceinline__ CropSrcNv12(const CropNv12Args& a, int li, int, int) : yp(a.y[li]), up(a.uv[li]), py(a.pitch[li][0]), puv(a.pitch[li][1]), k(a.c) {}
+    __device__ __forceinline__ Pixel pixel(int y, int x) const { return nv12_pixel(yp, up, py, puv, y, x, k); }
+    __device__ __forceinline__ float chan(Pixel t, int c) const { return nv12_chan(t, c); }
+};
+
+template <int ODT, int PX>
+__global__ __launch_bounds__(256) void crop_resize_nv12_kernel(const CropNv12Args a) {
+    crop_resize_body<CropSrcNv12, ODT, PX>(a);
+}
+
+// the frame rules of ops.nv12_planes: even sides >= 2, even pitches >= the width, a 2-byte-aligned chroma plane
+static int nv12_frame_ok(const char* who, int i, const void* y, const void* uv, int h, int w, int py, int puv) {
+    YMI_REQUIRE(y && uv, "%s: frame %d has a null plane", who, i);
+    YMI_REQUIRE(((uintptr_t)uv & 1) == 0, "%s: the CbCr plane of frame %d is not 2-byte aligned", who, i);
+    YMI_REQUIRE(h >= 2 && w >= 2 && (h & 1) == 0 && (w & 1) == 0 && (int64_t)h * w < ((int64_t)1 << 31), "%s: frame %d is %dx%d: NV12 sides are even and >= 2", who, i, h, w);
+    YMI_REQUIRE(py >= w && puv >= w && ((py | puv) & 1) == 0, "%s: frame %d: pitches %d / %d must be even and >= the width %d", who, i, py, puv, w);
+    return YMI_OK;
+}
+
 static bool nv12_coef(int matrix, int range, Nv12Coef& k) {
     if ((unsigned)matrix > 1u || (unsigned)range > 1u) return false;
     const int* c = NV12_COEF[matrix][range];
@@ -459,4 +622,114 @@ extern "C" int ymi_nv12_to_rgb(const void* y, const void* uv, int pitch_y, int p
     hipLaunchKernelGGL(nv12_to_rgb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)y, (const unsigned char*)uv,
                        pitch_y, pitch_uv, h, w, k, (unsigned char*)rgb, dword_ok);
     return check_launch("nv12_to_rgb_kernel");
+}
+
+extern "C" int ymi_render_nv12(const ymi_render_nv12_desc* d, void* stream) {
+    YMI_REQUIRE(d != nullptr, "ymi_render_nv12: null descriptor");
+    YMI_REQUIRE(d->n >= 0 && d->k >= 0, "ymi_render_nv12: negative batch size %d or slab depth %d", d->n, d->k);
+    YMI_REQUIRE(d->k <= YMI_RENDER_MAX_K, "ymi_render_nv12: slab depth %d above YMI_RENDER_MAX_K = %d", d->k, YMI_RENDER_MAX_K);
+    if (d->n == 0) return YMI_OK;
+    YMI_REQUIRE(d->y && d->uv && d->pitch && d->hw && d->lw && d->fs && d->boxes && d->scores && d->labels && d->counts && d->colors && d->status,
+                "ymi_render_nv12: null buffer (planes, pitches, sizes, lw, fs, boxes, scores, labels, counts, colors or status)");
+    YMI_REQUIRE(d->m >= 1 && d->num_classes >= 1, "ymi_render_nv12: %d colours (m) or %d classes, below 1", d->m, d->num_classes);
+    YMI_REQUIRE((unsigned)d->matrix <= 1u && (unsigned)d->range <= 1u, "ymi_render_nv12: bad matrix %d / range %d", d->matrix, d->range);
+    for (int c = 0; c < 3; ++c) YMI_REQUIRE(d->txt_color[c] >= 0 && d->txt_color[c] <= 255, "ymi_render_nv12: txt_color[%d] = %d outside 0..255", c, d->txt_color[c]);
+    for (int i = 0; i < d->n; ++i) {   // every frame before the first launch
+        const int rc = nv12_frame_ok("ymi_render_nv12", i, d->y[i], d->uv[i], d->hw[2 * i], d->hw[2 * i + 1], d->pitch[2 * i], d->pitch[2 * i + 1]);
+        if (rc != YMI_OK) return rc;
+        YMI_REQUIRE(d->lw[i] >= 1 && d->lw[i] <= 65535, "ymi_render_nv12: lw[%d] = %d outside [1, 65535]", i, d->lw[i]);
+        YMI_REQUIRE(d->fs[i] >= 1 && d->fs[i] <= 65535, "ymi_render_nv12: fs[%d] = %d outside [1, 65535]", i, d->fs[i]);
+    }
+    const size_t lds = render_nv12_lds(d->k);
+    for (int base = 0; base < d->n; base += NV12_MAX) {
+        RenderNv12Args a;
+        a.img_n = d->n - base < NV12_MAX ? d->n - base : NV12_MAX;
+        int64_t blocks = 0;
+        for (int i = 0; i < a.img_n; ++i) {
+            const int h = d->hw[2 * (base + i)], w = d->hw[2 * (base + i) + 1];
+            a.y[i] = (unsigned char*)d->y[base + i];
+            a.uv[i] = (unsigned char*)d->uv[base + i];
+            a.pitch[i][0] = d->pitch[2 * (base + i)];
+            a.pitch[i][1] = d->pitch[2 * (base + i) + 1];
+            a.hw[i][0] = h;
+            a.hw[i][1] = w;
+            a.lwfs[i][0] = d->lw[base + i];
+            a.lwfs[i][1] = d->fs[base + i];
+            blocks += (int64_t)cdiv(w, RD_TW) * cdiv(h, RD_TH);
+            a.tile_end[i] = (int)blocks;
+            YMI_REQUIRE(blocks < ((int64_t)1 << 31), "ymi_render_nv12: %lld workgroups in one launch", (long long)blocks);
+        }
+        a.boxes = d->boxes; a.scores = d->scores; a.labels = d->labels; a.counts = d->counts; a.names = d->names; a.colors = d->colors; a.status = d->status;
+        a.img_base = base; a.k = d->k; a.m = d->m; a.num_classes = d->num_classes; a.draw_labels = d->draw_labels ? 1 : 0; a.draw_conf = d->draw_conf ? 1 : 0;
+        a.txt = (uint32_t)d->txt_color[0] | ((uint32_t)d->txt_color[1] << 8) | ((uint32_t)d->txt_color[2] << 16);
+        a.c.yoff = d->range == YMI_NV12_LIMITED ? 16 : 0;
+        for (int j = 0; j < 9; ++j) a.c.c[j] = YCC_COEF[d->matrix][d->range][j];
+        hipLaunchKernelGGL(render_nv12_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, a);
+        const int rc = check_launch("render_nv12_kernel");
+        if (rc != YMI_OK) return rc;
+    }
+    return YMI_OK;
+}
+
+extern "C" int ymi_crop_resize_nv12(const ymi_crop_nv12_desc* d, void* stream) {
+    YMI_REQUIRE(d != nullptr, "ymi_crop_resize_nv12: null descriptor");
+    YMI_REQUIRE(d->n >= 0 && d->k >= 0, "ymi_crop_resize_nv12: negative batch size %d or slab depth %d", d->n, d->k);
+    YMI_REQUIRE(d->total && (d->n == 0 || (d->y && d->uv && d->pitch && d->hw && d->counts && (d->boxes || d->k == 0))),
+                "ymi_crop_resize_nv12: null buffer (planes, pitches, sizes, boxes, counts or total)");
+    YMI_REQUIRE(d->cap >= 0, "ymi_crop_resize_nv12: negative capacity %d", d->cap);
+    YMI_REQUIRE(d->cap == 0 || (d->crops && d->index), "ymi_crop_resize_nv12: null output buffer (crops or index) with capacity %d", d->cap);
+    YMI_REQUIRE(d->out_h >= 1 && d->out_w >= 1, "ymi_crop_resize_nv12: output size %d x %d below 1", d->out_h, d->out_w);
+    YMI_REQUIRE(d->out_dtype == YMI_F16 || d->out_dtype == YMI_BF16 || d->out_dtype == YMI_F32, "ymi_crop_resize_nv12: unsupported out_dtype %d (F16 / BF16 / F32)", d->out_dtype);
+    CropNv12Args a;
+    YMI_REQUIRE(nv12_coef(d->matrix, d->range, a.c), "ymi_crop_resize_nv12: bad matrix %d / range %d", d->matrix, d->range);
+    const float big = 3.0e38f;
+    YMI_REQUIRE(fabsf(d->gain) <= big && fabsf(d->pad) <= big, "ymi_crop_resize_nv12: gain and pad must be finite");
+    if (d->normalize)
+        for (int c = 0; c < 3; ++c)
+            YMI_REQUIRE(fabsf(d->mean[c]) <= big && fabsf(d->std[c]) <= big && d->std[c] != 0.f, "ymi_crop_resize_nv12: std[%d] is 0 (or mean / std not finite)", c);
+    for (int i = 0; i < d->n; ++i) {
+        const int rc = nv12_frame_ok("ymi_crop_resize_nv12", i, d->y[i], d->uv[i], d->hw[2 * i], d->hw[2 * i + 1], d->pitch[2 * i], d->pitch[2 * i + 1]);
+        if (rc != YMI_OK) return rc;
+    }
+    YMI_REQUIRE((int64_t)d->n * d->k < ((int64_t)1 << 31) && (int64_t)d->out_h * d->out_w < ((int64_t)1 << 31), "ymi_crop_resize_nv12: n * k or out_h * out_w does not fit 31 bits");
+    // the launch geometry of ymi_crop_resize: four pixels per thread where a row is a whole number of 4-pixel groups and the stores are aligned (YOLORT_AMD_CROP=pixel: one)
+    const char* env = getenv("YOLORT_AMD_CROP");
+    const size_t esz = d->out_dtype == YMI_F32 ? 4 : 2;
+    const bool wide = d->out_w % 4 == 0 && ((uintptr_t)d->crops & (4 * esz - 1)) == 0 && !(env && !strcmp(env, "pixel"));
+    const int64_t tiles = ((int64_t)d->out_h * (d->out_w / (wide ? 4 : 1)) + 255) / 256;
+    a.boxes = d->boxes; a.counts = d->counts; a.crops = d->crops; a.index = d->index; a.total = d->total;
+    a.n = d->n; a.k = d->k; a.cap = d->cap; a.out_h = d->out_h; a.out_w = d->out_w; a.tiles = (int)tiles;
+    a.square = d->square ? 1 : 0; a.normalize = d->normalize ? 1 : 0;
+    a.gain = d->gain; a.pad = d->pad;
+    for (int c = 0; c < 3; ++c) { a.mean[c] = d->mean[c]; a.std[c] = d->std[c]; }
+    for (int base = 0; base < d->n || base == 0; base += NV12_MAX) {   // every launch reads the WHOLE counts array: row offsets are global; the first one writes total[]
+        a.img_base = base;
+        a.img_n = d->n - base < NV12_MAX ? d->n - base : NV12_MAX;
+        for (int i = 0; i < a.img_n; ++i) {
+            a.y[i] = (const unsigned char*)d->y[base + i];
+            a.uv[i] = (const unsigned char*)d->uv[base + i];
+            a.pitch[i][0] = d->pitch[2 * (base + i)];
+            a.pitch[i][1] = d->pitch[2 * (base + i) + 1];
+            a.hw[i][0] = d->hw[2 * (base + i)];
+            a.hw[i][1] = d->hw[2 * (base + i) + 1];
+        }
+        int64_t blocks = (int64_t)a.img_n * d->k * tiles;
+        if (d->cap == 0 || blocks == 0) blocks = base == 0 ? 1 : 0;   // nothing to cut: one workgroup of the first launch still writes total[]
+        if (blocks == 0) continue;
+        YMI_REQUIRE(blocks < ((int64_t)1 << 31), "ymi_crop_resize_nv12: %lld workgroups in one launch", (long long)blocks);
+        dim3 grid((unsigned)blocks), block(256);
+        hipStream_t s = (hipStream_t)stream;
+#define YMI_CROP_NV12(ODT_)                                                              \
+    if (wide) hipLaunchKernelGGL((crop_resize_nv12_kernel<ODT_, 4>), grid, block, 0, s, a); \
+    else hipLaunchKernelGGL((crop_resize_nv12_kernel<ODT_, 1>), grid, block, 0, s, a);
+        switch (d->out_dtype) {
+            case YMI_F16: YMI_CROP_NV12(YMI_F16) break;
+            case YMI_BF16: YMI_CROP_NV12(YMI_BF16) break;
+            default: YMI_CROP_NV12(YMI_F32) break;
+        }
+#undef YMI_CROP_NV12
+        const int rc = check_launch("crop_resize_nv12_kernel");
+        if (rc != YMI_OK) return rc;
+    }
+    return YMI_OK;
 }

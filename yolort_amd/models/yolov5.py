@@ -262,6 +262,63 @@ class YOLOv5(nn.Module):
             raise YmiError(f"render: the kernel reports status {status} (bad count 1, stale row 2, label outside the names 4)")
         return out
 
+    def _slab(self, detections, n: int, dev, what: str):
+        """the List[Dict] of forward() packed into the slab form of the ops: (boxes (n, K, 4), scores (n, K), labels (n, K), counts (n,), the lengths)"""
+        if len(detections) != n:
+            raise ValueError(f"{what}: {len(detections)} detection dicts for {n} frames")
+        lens = [int(d["boxes"].shape[0]) for d in detections]
+        k = max(lens + [1])
+        boxes = torch.zeros((n, k, 4), device=dev, dtype=torch.float32)
+        scores = torch.zeros((n, k), device=dev, dtype=torch.float32)
+        labels = torch.zeros((n, k), device=dev, dtype=torch.int64)
+        for i, d in enumerate(detections):
+            if lens[i]:
+                boxes[i, : lens[i]] = d["boxes"].to(device=dev, dtype=torch.float32)
+                scores[i, : lens[i]] = d["scores"].to(device=dev, dtype=torch.float32)
+                labels[i, : lens[i]] = d["labels"].to(device=dev, dtype=torch.int64)
+        return boxes, scores, labels, torch.tensor(lens, dtype=torch.int32).to(dev), lens
+
+    @torch.no_grad()
+    def crop_nv12(self, frames, detections: Optional[List[Dict[str, Tensor]]] = None, size: Tuple[int, int] = (224, 224), **kw: Any) -> List[Tensor]:
+        """crop() for NV12 video frames (ops.nv12_planes): the detected objects cut straight out of the Y / CbCr planes by ONE launch (`ops.crop_detections_nv12`, whose
+        keyword arguments -- matrix, full_range, gain, pad, square, mean, std, dtype -- pass through; matrix / full_range also reach forward_nv12 when `detections` is
+        None) and split by the counts after one synchronisation.  Per frame a (len(detections[i]), 3, size[0], size[1]) tensor: exactly crop() of the converted frames."""
+        from .. import ops
+        frames = [frames[i] for i in range(len(frames))]
+        if detections is None:
+            detections = self.forward_nv12(frames, **{key: kw[key] for key in ("matrix", "full_range") if key in kw})
+        if "capacity" in kw:
+            raise ValueError("crop_nv12: the capacity is the number of detections")
+        n = len(frames)
+        if n == 0:
+            return []
+        boxes, _, _, counts, lens = self._slab(detections, n, ops.nv12_planes(frames[0])[0].device, "crop_nv12")
+        crops, _, total = ops.crop_detections_nv12(frames, boxes, counts, size, capacity=sum(lens), **kw)
+        written, status = total.tolist()   # the one synchronisation
+        if status != 0 or written != sum(lens):
+            raise YmiError(f"crop_nv12: the kernel wrote {written} of {sum(lens)} crops (status {status})")
+        return list(torch.split(crops, lens))
+
+    @torch.no_grad()
+    def render_nv12(self, frames, detections: Optional[List[Dict[str, Tensor]]] = None, names: Optional[Sequence[str]] = None, **kw: Any):
+        """render() for NV12 video frames (ops.nv12_planes): the detections drawn straight into the Y / CbCr planes, the form a hardware encoder takes, by ONE launch
+        (`ops.draw_detections_nv12`, whose keyword arguments -- matrix, full_range, colors, line_width, font_scale, labels_on, conf, txt_color, inplace -- pass through;
+        matrix / full_range also reach forward_nv12 when `detections` is None); ONE status word is read back.  Returns the annotated frames: packed (3h/2, w) copies
+        unless inplace=True.  The text has no parity with the reference, as in render()."""
+        from .. import ops
+        frames = [frames[i] for i in range(len(frames))]
+        if detections is None:
+            detections = self.forward_nv12(frames, **{key: kw[key] for key in ("matrix", "full_range") if key in kw})
+        n = len(frames)
+        if n == 0:
+            return []
+        boxes, scores, labels, counts, _ = self._slab(detections, n, ops.nv12_planes(frames[0])[0].device, "render_nv12")
+        out, status = ops.draw_detections_nv12(frames, boxes, scores, labels, counts, names=names, **kw)
+        status = int(status.item())   # the one synchronisation
+        if status != 0:
+            raise YmiError(f"render_nv12: the kernel reports status {status} (bad count 1, stale row 2, label outside the names 4)")
+        return out
+
     def default_loader(self, img_path: str) -> Tensor:
         """RGB uint8 image as decoded, (H, W, 3); the permute and the /255 of the reference (yolov5.py:218-228) are fused into
         the letterbox kernel's interleaved-uint8 path (decode stays on the host, PIL)."""

@@ -275,6 +275,61 @@ def crop_detections(images: Sequence[Tensor], boxes: Tensor, counts: Tensor, siz
     return crops, index, total
 
 
+def _nv12_tables(planes):
+    """the host arrays every NV12 descriptor takes: plane pointers, n x {pitch_y, pitch_uv}, n x {h, w}"""
+    n = len(planes)
+    ys = (C.c_void_p * max(n, 1))(*[p[0].data_ptr() for p in planes])
+    uvs = (C.c_void_p * max(n, 1))(*[p[1].data_ptr() for p in planes])
+    pitch = (C.c_int32 * max(2 * n, 1))(*[v for p in planes for v in (p[0].stride(0), p[1].stride(0))])
+    hw = (C.c_int32 * max(2 * n, 1))(*[v for p in planes for v in (p[2], p[3])])
+    return ys, uvs, pitch, hw
+
+
+def crop_detections_nv12(frames, boxes: Tensor, counts: Tensor, size, *, matrix: str = "bt601", full_range: bool = False, gain: float = 1.02, pad: float = 10,
+                         square: bool = False, mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None, dtype: torch.dtype = torch.float16,
+                         capacity: Optional[int] = None):
+    """crop_detections for NV12 video frames (see nv12_planes: packed (3h/2, w) buffers or (y, uv) pairs of pitched planes), in one launch per batch
+    (ymi_crop_resize_nv12): the taps are fetched from the planes and converted on the fly (`matrix` "bt601" / "bt709", limited or full range), so no RGB copy of a
+    frame is made.  -> (crops, index, total), BIT FOR BIT crop_detections([nv12_to_rgb(f) for f in frames], ...) with the same keyword arguments.  No
+    synchronisation, no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    planes = [nv12_planes(frames[i]) for i in range(len(frames))]
+    n = len(planes)
+    m, r = _nv12_params(matrix, full_range)
+    if not boxes.is_cuda or not counts.is_cuda or not all(p[0].is_cuda for p in planes):
+        raise YmiError("crop_detections_nv12 runs on an MI355X only (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4 or tuple(counts.shape) != (n,):
+        raise YmiError(f"crop_detections_nv12: expected the slab (n, K, 4) / (n,) for {n} frames, got {tuple(boxes.shape)} {tuple(counts.shape)}")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise YmiError(f"crop_detections_nv12: dtype must be float16, bfloat16 or float32, got {dtype}")
+    if (mean is None) != (std is None):
+        raise ValueError("crop_detections_nv12: mean and std go together")
+    out_h, out_w = int(size[0]), int(size[1])
+    k = int(boxes.shape[1])
+    cap = n * k if capacity is None else int(capacity)
+    dev = boxes.device
+    d = _lib.CropNv12Desc()
+    ys, uvs, pitch, hw = _nv12_tables(planes)
+    b = boxes.detach().to(torch.float32).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    crops = torch.empty((max(cap, 0), 3, max(out_h, 0), max(out_w, 0)), device=dev, dtype=dtype)
+    index = torch.empty((max(cap, 0), 6), device=dev, dtype=torch.int32)
+    total = torch.empty(2, device=dev, dtype=torch.int32)
+    d.y, d.uv = C.cast(ys, C.POINTER(C.c_void_p)), C.cast(uvs, C.POINTER(C.c_void_p))
+    d.pitch, d.hw = C.cast(pitch, C.POINTER(C.c_int32)), C.cast(hw, C.POINTER(C.c_int32))
+    d.boxes, d.counts, d.crops, d.index, d.total = b.data_ptr(), c.data_ptr(), crops.data_ptr(), index.data_ptr(), total.data_ptr()
+    d.gain, d.pad, d.square, d.normalize = float(gain), float(pad), 1 if square else 0, 0 if mean is None else 1
+    if mean is not None:
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("crop_detections_nv12: mean and std have one value per channel")
+        for i in range(3):
+            d.mean[i], d.std[i] = float(mean[i]), float(std[i])
+    d.n, d.k, d.cap, d.out_h, d.out_w = n, k, cap, out_h, out_w
+    d.matrix, d.range, d.out_dtype = m, r, _lib.dtype_code(dtype)
+    check(lib.ymi_crop_resize_nv12(C.byref(d), _lib.stream_ptr()), "ymi_crop_resize_nv12")
+    return crops, index, total
+
+
 # The default colours of draw_detections, the project's own: 20 hues in steps of 7 / 20 of the colour circle (neighbouring classes far apart), saturation 0.85 / 0.6
 # and value 1.0 / 0.8 alternating -- RGB.  A detection of class c has DEFAULT_COLORS[c % 20].
 DEFAULT_COLORS = ((255, 38, 38), (102, 255, 117), (65, 31, 204), (204, 118, 82), (38, 255, 125), (178, 102, 255), (204, 135, 31), (82, 204, 167), (212, 38, 255), (255, 240, 102),
@@ -378,6 +433,64 @@ def draw_detections(images: Sequence[Tensor], boxes: Tensor, scores: Tensor, lab
     d.draw_labels, d.draw_conf, d.n, d.k = int(bool(labels_on)), int(bool(conf)), n, k
     check(lib.ymi_render(C.byref(d), _lib.stream_ptr()), "ymi_render")
     return images, status
+
+
+def draw_detections_nv12(frames, boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, *, matrix: str = "bt601", full_range: bool = False,
+                         names: Optional[Sequence[str]] = None, colors: Optional[Sequence[Sequence[int]]] = None, line_width=None, font_scale=None, labels_on: bool = True,
+                         conf: bool = True, txt_color: Sequence[int] = (255, 255, 255), inplace: bool = False):
+    """draw_detections for NV12 video frames (see nv12_planes: packed (3h/2, w) buffers or (y, uv) pairs of pitched planes): every detection of the slab drawn
+    straight into the Y and CbCr planes, the form a hardware encoder takes, in one launch per batch (ymi_render_nv12, include/yolort_amd.h).  Which detection decides a
+    luma pixel, and whether as outline, label background or glyph, is draw_detections's rule unchanged (the text has no parity with the reference either); the pixel
+    gets the Y of its RGB colour under the integer RGB -> YCbCr contract of the header (`matrix` "bt601" / "bt709", limited or full range), and a chroma pair one of
+    whose four luma pixels is decided gets the (Cb, Cr) of the first decided one in raster order.  Nothing else is written: untouched pixels, pairs, pitch padding and
+    tiles keep the decoder's bytes.  -> (frames, status): with inplace=True the inputs themselves; otherwise copies -- a packed frame as its clone, a (y, uv) pair as ONE
+    packed contiguous (3h/2, w) frame.  The other keyword arguments, the defaults (`render_defaults(h, w)`), K <= 1024 and the status bits are draw_detections's.
+    NO synchronisation, no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    frames = [frames[i] for i in range(len(frames))]
+    n = len(frames)
+    planes = [nv12_planes(f) for f in frames]
+    mat, rng = _nv12_params(matrix, full_range)
+    if not all(t.is_cuda for t in (boxes, scores, labels, counts)) or not all(p[0].is_cuda for p in planes):
+        raise YmiError("draw_detections_nv12 runs on an MI355X only (no CPU fallback)")
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(boxes.shape[:2]) or tuple(counts.shape) != (n,):
+        raise YmiError(f"draw_detections_nv12: expected the slab (n, K, 4) / (n, K) / (n, K) / (n,) for {n} frames, got {tuple(boxes.shape)} {tuple(scores.shape)} {tuple(labels.shape)} {tuple(counts.shape)}")
+    if not inplace:
+        frames = [torch.cat([p[0], p[1]]) for p in planes]   # packed and contiguous, whatever came in
+        planes = [nv12_planes(f) for f in frames]
+    k = int(boxes.shape[1])
+    dev = boxes.device
+
+    def per_image(value, which):
+        if value is None:
+            return [render_defaults(p[2], p[3])[which] for p in planes]
+        return [int(v) for v in value] if isinstance(value, (list, tuple)) else [int(value)] * n
+
+    lws, fss = per_image(line_width, 0), per_image(font_scale, 1)
+    if len(lws) != n or len(fss) != n:
+        raise ValueError("draw_detections_nv12: line_width / font_scale are one value or one per frame")
+    d = _lib.RenderNv12Desc()
+    ys, uvs, pitch, hw = _nv12_tables(planes)
+    lw_a, fs_a = (C.c_int32 * max(n, 1))(*lws), (C.c_int32 * max(n, 1))(*fss)
+    b = boxes.detach().to(torch.float32).contiguous()
+    s = scores.detach().to(torch.float32).contiguous()
+    lab = labels.detach().to(torch.int64).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    table = _render_table("names", tuple(str(v) for v in names), dev) if names is not None else None
+    palette = _render_table("colors", tuple(int(v) for row in (DEFAULT_COLORS if colors is None else colors) for v in row), dev)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    d.y, d.uv = C.cast(ys, C.POINTER(C.c_void_p)), C.cast(uvs, C.POINTER(C.c_void_p))
+    d.pitch, d.hw = C.cast(pitch, C.POINTER(C.c_int32)), C.cast(hw, C.POINTER(C.c_int32))
+    d.lw, d.fs = C.cast(lw_a, C.POINTER(C.c_int32)), C.cast(fs_a, C.POINTER(C.c_int32))
+    d.boxes, d.scores, d.labels, d.counts, d.status = b.data_ptr(), s.data_ptr(), lab.data_ptr(), c.data_ptr(), status.data_ptr()
+    d.names, d.colors, d.m = (table.data_ptr() if table is not None else None), palette.data_ptr(), int(palette.shape[0])
+    for i in range(3):
+        d.txt_color[i] = int(txt_color[i])
+    d.num_classes = int(table.shape[0]) if table is not None else 2 ** 31 - 1
+    d.matrix, d.range = mat, rng
+    d.draw_labels, d.draw_conf, d.n, d.k = int(bool(labels_on)), int(bool(conf)), n, k
+    check(lib.ymi_render_nv12(C.byref(d), _lib.stream_ptr()), "ymi_render_nv12")
+    return frames, status
 
 
 def slab_to_list(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Sequence[int]) -> List[Dict[str, Tensor]]:
