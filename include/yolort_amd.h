@@ -325,6 +325,77 @@ typedef struct ymi_crop_nv12_desc {
 } ymi_crop_nv12_desc;
 int ymi_crop_resize_nv12(const ymi_crop_nv12_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Second-stage classification: the tail of a classifier over the crops -- global average pool, Linear (, Hardswish, Linear) -- and the last line of
+ * apply_classifier on the slab.  Replaces the avgpool + classifier of DarkNetV6 / DarkNetV4._forward_impl (yolort/models/darknetv6.py:98-105, :116-121;
+ * Dropout is the identity in eval), Classify.forward (yolort/v5/models/common.py:679-689: AdaptiveAvgPool2d(1) per map, torch.cat, a 1x1 Conv2d with bias,
+ * Flatten) and `x[i] = x[i][pred_cls1 == pred_cls2]` of apply_classifier (yolort/v5/utils/general.py:721-722).
+ * ymi_classify_head (csrc/classify_head.hip, pool_fc_kernel: a workgroup owns 32 rows and keeps their whole pooled block in LDS, a wave owns 32-column slices
+ * of the output and streams their weights through registers into the 32x32x16 MFMA):
+ *   maps[i]   device NHWC views (n, hw[i] pixels, c[i] channels, pixel stride cs[i] elements) of `dtype` (YMI_F16 / YMI_BF16), 1 .. 4 of them; c[i] and cs[i]
+ *             multiples of 8, pointers 16-byte aligned, sum of c[i] = K <= YMI_CLASSIFY_MAX_K.  The channel ranges sit side by side along K (torch.cat(..., 1)).
+ *   w1, b1    device (ceil(n1 / 32) * 32, K) of `dtype`, K-contiguous -- nn.Linear's own layout, a 1x1 Conv2d weight reshaped -- rows >= n1 ZERO; fp32 bias of
+ *             the same padded length, entries >= n1 zero.  w2, b2 likewise with K = n1 (YMI_CLASSIFY_HIDDEN_LOGITS only; n1 a multiple of 8 then).
+ *   hidden    device (n, n1) of `dtype`, workspace of the two-stage mode; logits device (n, n_last) fp32, n_last = n1 (YMI_CLASSIFY_LOGITS) or n2.
+ * Arithmetic: pooled[r][k] = (sum over the pixels IN ORDER, fp32) * (1 / hw rounded to fp32), rounded ONCE to `dtype` (what AdaptiveAvgPool2d returns in that
+ * dtype); every product of 16-bit operands is exact and accumulated in fp32 over K (MFMA order); + bias in fp32.  YMI_CLASSIFY_LOGITS: that value is the logit.
+ * YMI_CLASSIFY_HIDDEN_LOGITS: Hardswish x * min(max(x + 3, 0), 6) / 6 in fp32 (a true division), rounded ONCE to `dtype`, then the second product + bias.
+ * Grid (ceil(n / 32), n_split): n_split = 0 lets the launcher spread the output slices of few rows over the CUs (CUs / row blocks, at most one slice per
+ * workgroup) and use 1 for many; > 0 forces it (so does YOLORT_AMD_CLASSIFY_NSPLIT).  The logits do not depend on it, bit for bit: a slice's K order is fixed.
+ * Nothing outside hidden's and logits' n rows is written, nothing outside a view or a padded weight matrix is read.  n = 0 launches nothing.
+ * ymi_second_stage_filter (second_stage_filter_kernel: a workgroup per image, a wave per detection):
+ *   boxes (n, k, 4) fp32, scores (n, k) fp32, labels (n, k) int64, counts (n) int32: the slab as the top-k kernel writes it; logits (cap, nc2) fp32 in
+ *   ymi_crop_resize's row order (row of detection j of image i = the exclusive prefix of the clamped counts + j; the crop's index is not read) with its total;
+ *   class_map int32[nc2]: second-stage class -> detector label, NULL = the identity.
+ *   cls2[i][j] = arg-max of the row: the LOWEST index among the maxima, a NaN greater than every number (the first NaN wins) -- torch.argmax's rule on the CPU;
+ *   -1 for a slot at or past its count and for a row at or past min(total[0], cap).  A detection is kept iff class_map[cls2] == label.  Kept rows are
+ *   compacted in slab order into out_boxes / out_scores / out_labels (same shapes, must not alias the inputs; slots past the new count are ZERO), out_counts (n).
+ *   status[0], WRITTEN by every call: YMI_FILTER_STATUS_BAD_COUNT (a count below 0 -- the image is skipped -- or above k -- clamped), _TOTAL (total[0] differs
+ *   from min(sum of the clamped counts, cap)), _CAPACITY (the sum exceeds cap: the rows past it are dropped).
+ * k <= YMI_FILTER_MAX_K; any number of images in one launch.  Neither call allocates or synchronises; both are ordered on `stream` and may be captured; no
+ * atomics.  YMI_EINVAL (nothing is launched): a null or misaligned buffer, a shape outside the limits above, a dtype other than F16 / BF16.
+ * ABI stays 6: two new structs, two new functions.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_CLASSIFY_MAX_MAPS 4
+#define YMI_CLASSIFY_MAX_K 2496        /* 32 rows x (K rounded up to 64, + 8) 16-bit values fit 160 KiB of LDS */
+#define YMI_CLASSIFY_LOGITS 0          /* pooled maps -> logits (Classify) */
+#define YMI_CLASSIFY_HIDDEN_LOGITS 1   /* pooled maps -> Hardswish hidden -> logits (DarkNetV4 / V6) */
+typedef struct ymi_classify_desc {
+    const void* maps[YMI_CLASSIFY_MAX_MAPS];
+    int32_t hw[YMI_CLASSIFY_MAX_MAPS], c[YMI_CLASSIFY_MAX_MAPS], cs[YMI_CLASSIFY_MAX_MAPS];
+    const void* w1;
+    const float* b1;
+    const void* w2;
+    const float* b2;
+    void* hidden;
+    float* logits;
+    int32_t num_maps, n, n1, n2;
+    int32_t dtype, mode, n_split;
+    int32_t reserved;
+} ymi_classify_desc;
+int ymi_classify_head(const ymi_classify_desc* d, void* stream);
+#define YMI_FILTER_STATUS_BAD_COUNT 1
+#define YMI_FILTER_STATUS_TOTAL 2
+#define YMI_FILTER_STATUS_CAPACITY 4
+#define YMI_FILTER_MAX_K 32768
+typedef struct ymi_filter_desc {
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const float* logits;
+    const int32_t* total;
+    const int32_t* class_map;
+    float* out_boxes;
+    float* out_scores;
+    int64_t* out_labels;
+    int32_t* out_counts;
+    int32_t* cls2;
+    int32_t* status;
+    int32_t n, k, cap, nc2;
+} ymi_filter_desc;
+int ymi_second_stage_filter(const ymi_filter_desc* d, void* stream);
+
 /* NCHW (n,c,h,w) -> NHWC view and back (module-level API edges; not on the fused path). */
 int ymi_nchw_to_nhwc(const void* x, int n, int c, int h, int w, int in_dtype, void* y, int y_cstride,
                      int c_pad, int out_dtype, void* stream);

@@ -194,6 +194,29 @@ class CropNv12Desc(C.Structure):
     ]
 
 
+class ClassifyDesc(C.Structure):
+    """ymi_classify_desc: up to four NHWC maps, the packed weights and biases of one or two linear layers, the outputs and the mode of one ymi_classify_head call"""
+    _fields_ = [
+        ("maps", C.c_void_p * 4), ("hw", C.c_int32 * 4), ("c", C.c_int32 * 4), ("cs", C.c_int32 * 4),
+        ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p), ("hidden", C.c_void_p), ("logits", C.c_void_p),
+        ("num_maps", C.c_int32), ("n", C.c_int32), ("n1", C.c_int32), ("n2", C.c_int32),
+        ("dtype", C.c_int32), ("mode", C.c_int32), ("n_split", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class FilterDesc(C.Structure):
+    """ymi_filter_desc: the detection slab, the second-stage logits with the crop's total, the filtered slab, cls2 and the status word of one ymi_second_stage_filter call"""
+    _fields_ = [
+        ("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p), ("logits", C.c_void_p), ("total", C.c_void_p),
+        ("class_map", C.c_void_p), ("out_boxes", C.c_void_p), ("out_scores", C.c_void_p), ("out_labels", C.c_void_p), ("out_counts", C.c_void_p),
+        ("cls2", C.c_void_p), ("status", C.c_void_p),
+        ("n", C.c_int32), ("k", C.c_int32), ("cap", C.c_int32), ("nc2", C.c_int32),
+    ]
+
+
+CLASSIFY_MAX_MAPS, CLASSIFY_MAX_K, CLASSIFY_LOGITS, CLASSIFY_HIDDEN_LOGITS = 4, 2496, 0, 1   # YMI_CLASSIFY_*
+FILTER_STATUS_BAD_COUNT, FILTER_STATUS_TOTAL, FILTER_STATUS_CAPACITY, FILTER_MAX_K = 1, 2, 4, 32768   # YMI_FILTER_*
+
 VIEW_PAD = 0.447  # YMI_VIEW_PAD: the pad value of a view canvas (scale_img's F.pad value)
 TTA_SCALES, TTA_FLIPS = (1.0, 0.83, 0.67), (False, True, False)   # ultralytics' _forward_augment (yolort/v5/models/yolo.py:154-155): scales, left-right mirror
 
@@ -272,6 +295,8 @@ _SIGS = {
     "ymi_render": (C.c_int, [C.POINTER(RenderDesc), C.c_void_p]),
     "ymi_render_nv12": (C.c_int, [C.POINTER(RenderNv12Desc), C.c_void_p]),
     "ymi_crop_resize_nv12": (C.c_int, [C.POINTER(CropNv12Desc), C.c_void_p]),
+    "ymi_classify_head": (C.c_int, [C.POINTER(ClassifyDesc), C.c_void_p]),
+    "ymi_second_stage_filter": (C.c_int, [C.POINTER(FilterDesc), C.c_void_p]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

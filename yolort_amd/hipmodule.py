@@ -167,6 +167,14 @@ class HipModule(nn.Module):
             return self._forward_on_device(xs, is_list)
 
     def _forward_on_device(self, xs, is_list):
+        outs = self._run_plan(xs, is_list)
+        odt = xs[0].dtype if xs[0].dtype.is_floating_point else torch.float32
+        if isinstance(outs, View):
+            return view_to_nchw(outs, odt)
+        return [view_to_nchw(o, odt) for o in outs]
+
+    def _run_plan(self, xs, is_list):
+        """the cached plan of these input shapes, run on `xs` -> its output View(s): the plan's own buffers, valid until the next run"""
         cdt = compute_dtype_of(self)
         key = (tuple(tuple(t.shape) for t in xs), cdt, xs[0].device.index, weights_signature(self))
         entry = self._plans.get(key)
@@ -184,7 +192,4 @@ class HipModule(nn.Module):
         for t, v in zip(xs, ins):
             nchw_to_view(plan, t, v.c, out=v)
         plan.run()
-        odt = xs[0].dtype if xs[0].dtype.is_floating_point else torch.float32
-        if isinstance(outs, View):
-            return view_to_nchw(outs, odt)
-        return [view_to_nchw(o, odt) for o in outs]
+        return outs

@@ -1,8 +1,8 @@
 """CSPDarknet of the r3.1 / r4.0 releases (reference yolort/models/darknetv4.py:32-219): Focus stem + 3 x [Conv k3 s2, block(n)] + Conv k3 s2 + SPP, block =
 BottleneckCSP (r3.1: Hardswish / LeakyReLU) or C3 (r4.0: SiLU).
 
-Only `.features` is on the inference path; the ImageNet classifier head (:99-105) is kept as plain parameter containers so `state_dict()` of a full DarkNetV4 matches the
-reference's, but it is never emitted.  The Focus stem runs as the 6 x 6 stride-2 convolution it is equivalent to (v5/models/common.py Focus): every stem kernel of the
+Only `.features` is on the detector's inference path; the ImageNet classifier head (:99-105) is kept as plain parameter containers so `state_dict()` of a full DarkNetV4
+matches the reference's, and `forward` runs it after `.features` (darknetv6.classifier_forward).  The Focus stem runs as the 6 x 6 stride-2 convolution it is equivalent to (v5/models/common.py Focus): every stem kernel of the
 r6.0 path applies unchanged.
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ from torch import nn
 
 from ..v5 import C3, SPP, BottleneckCSP, Conv, Focus
 from ._utils import _make_divisible
-from .darknetv6 import Features
+from .darknetv6 import Features, classifier_forward
 
 __all__ = ["DarkNetV4", "darknet_s_r3_1", "darknet_m_r3_1", "darknet_l_r3_1", "darknet_s_r4_0", "darknet_m_r4_0", "darknet_l_r4_0"]
 
@@ -56,7 +56,7 @@ class DarkNetV4(nn.Module):
                 m.eps, m.momentum = 1e-3, 0.03
 
     def forward(self, x):
-        raise NotImplementedError("the ImageNet classifier of DarkNetV4 is not part of the YOLOv5 inference path; use `.features`")
+        return classifier_forward(self, x)
 
 
 def _darknet_v4_conf(arch: str, pretrained: bool, progress: bool, *args: Any, **kwargs: Any) -> DarkNetV4:

@@ -1,17 +1,20 @@
 """CSPDarknet r6.0 body (reference yolort/models/darknetv6.py:31-199).
 
-Only `.features` (stem Conv(3,c,k=6,s=2,p=2) + 4 x [Conv k3 s2, C3]) is on the inference path; the
-reference's ImageNet classifier head (avgpool + classifier, :98-105) is kept as plain parameter
-containers so `state_dict()` of a full DarkNetV6 matches, but it is never emitted.
+Only `.features` (stem Conv(3,c,k=6,s=2,p=2) + 4 x [Conv k3 s2, C3]) is on the detector's inference
+path; the reference's ImageNet classifier head (avgpool + classifier, :98-105) is kept as plain
+parameter containers so `state_dict()` of a full DarkNetV6 matches.  `forward` -- the model as a
+second-stage classifier -- runs `.features`' plan and then the head as ops.classify_head.
 """
 from __future__ import annotations
 
 from typing import Any, Callable, List, Optional
 
-from torch import nn
+import torch
+from torch import Tensor, nn
 
+from .._lib import YmiError
 from ..engine import Plan, View
-from ..hipmodule import HipModule
+from ..hipmodule import HipModule, compute_dtype_of, weights_signature
 from ..v5 import C3, Conv
 from ._utils import _make_divisible
 
@@ -73,7 +76,32 @@ class DarkNetV6(nn.Module):
                 m.eps, m.momentum = 1e-3, 0.03
 
     def forward(self, x):
-        raise NotImplementedError("the ImageNet classifier of DarkNetV6 is not part of the YOLOv5 inference path; use `.features`")
+        return classifier_forward(self, x)
+
+
+def classifier_forward(model: nn.Module, x: Tensor) -> Tensor:
+    """The reference's `_forward_impl` (darknetv6.py:116-121, darknetv4.py alike) on the MI355X: `.features`' cached plan, then avgpool + classifier (Linear,
+    Hardswish, Dropout = identity in eval, Linear) as the two launches of ops.classify_head on the plan's NHWC output -- no NCHW round trip.  (n, 3, h, w) ->
+    (n, num_classes) logits in the input's floating dtype.  The packed weights are cached on the classifier's weights_signature, like plans."""
+    from .. import ops
+    if model.training:
+        raise NotImplementedError("yolort_amd implements the inference path only; call .eval() (training is out of scope)")
+    if not x.is_cuda:
+        raise YmiError("yolort_amd runs on an MI355X only: move the model and inputs to 'cuda' (there is no CPU fallback)")
+    if x.dim() != 4:
+        raise ValueError(f"expected an NCHW tensor, got shape {tuple(x.shape)}")
+    cdt = compute_dtype_of(model.features)
+    if torch.float32 in (cdt, getattr(model, "compute_dtype", None)):
+        raise YmiError("the classifier head computes in float16 or bfloat16: compute_dtype = torch.float32 (the parity mode) covers `.features` only")
+    with torch.cuda.device(x.device):
+        key = (cdt, x.device.index, weights_signature(model.classifier))
+        cached = model.__dict__.get("_ymi_head")
+        if cached is None or cached[0] != key:
+            fc1, fc2 = model.classifier[0], model.classifier[3]
+            cached = model.__dict__["_ymi_head"] = (key, ops.pack_linear(fc1.weight, fc1.bias, cdt), ops.pack_linear(fc2.weight, fc2.bias, cdt))
+        fmap = model.features._run_plan([x], False)
+        logits = ops.classify_head(fmap, cached[1], None, cached[2], dtype=cdt)
+    return logits.to(x.dtype if x.dtype.is_floating_point else torch.float32)
 
 
 def _darknet_v6_conf(arch: str, pretrained: bool, progress: bool, *args: Any, **kwargs: Any) -> DarkNetV6:

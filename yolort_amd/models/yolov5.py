@@ -229,6 +229,45 @@ class YOLOv5(nn.Module):
         return list(torch.split(crops, lens)) if n else []
 
     @torch.no_grad()
+    def classify(self, images: List[Tensor], classifier: nn.Module, detections: Optional[List[Dict[str, Tensor]]] = None, *, size: Tuple[int, int] = (224, 224),
+                 class_map: Optional[Tensor] = None, batch: int = 256, **crop_kw: Any) -> List[Dict[str, Tensor]]:
+        """Second-stage classification, the device form of the reference's apply_classifier (yolort/v5/utils/general.py:691-723): every detection is cut out
+        (`ops.crop_detections`), `classifier` -- a DarkNetV6 / DarkNetV4, or any module mapping (b, 3, h, w) crops to (b, nc2) logits on the device -- runs over
+        the crops in chunks of `batch` into one logits buffer, and `ops.second_stage_filter` keeps a detection iff the arg-max class (through `class_map`, second-stage
+        class -> detector label; None = the identity) equals its label.  -> the List[Dict] of the survivors, in their order, read back with ONE synchronisation.
+        `images`: the list forward() takes; `detections`: its List[Dict] (None: forward() runs first).  The crop defaults are apply_classifier's recipe (square=True,
+        gain=1.3, pad=30); crop_kw passes through to the crop op.  As there, the padding is in IMAGE pixels (the reference pads in canvas pixels before
+        scale_coords), so parity with the reference's rectangles is not claimed.  Without mean / std the crops are in [0, 1], as apply_classifier feeds its model.
+        forward() / predict() themselves are untouched."""
+        from .. import ops
+        images = [images[i] for i in range(len(images))]
+        if detections is None:
+            detections = self.forward(images)
+        n = len(images)
+        if n == 0:
+            return []
+        if "capacity" in crop_kw:
+            raise ValueError("classify: the capacity is the number of detections")
+        if batch < 1:
+            raise ValueError(f"classify: batch = {batch}")
+        dev = images[0].device
+        boxes, scores, labels, counts, lens = self._slab(detections, n, dev, "classify")
+        kw = {"square": True, "gain": 1.3, "pad": 30, **crop_kw}
+        crops, _, total = ops.crop_detections(images, boxes, counts, size, capacity=sum(lens), **kw)
+        logits = None
+        for r0 in range(0, sum(lens), batch):
+            out = classifier(crops[r0: r0 + batch])
+            if logits is None:
+                logits = torch.empty((sum(lens), out.shape[1]), device=dev, dtype=torch.float32)
+            logits[r0: r0 + batch] = out
+        if logits is None:   # no detections at all: nothing to filter
+            return [{"boxes": d["boxes"], "scores": d["scores"], "labels": d["labels"]} for d in detections]
+        ob, os_, ol, oc, _, status = ops.second_stage_filter(boxes, scores, labels, counts, logits, total, class_map=class_map)
+        kept = torch.cat([oc, status]).tolist()   # the one synchronisation
+        ops._raise_filter_status(kept[-1])
+        return [{"boxes": ob[i, : kept[i]], "scores": os_[i, : kept[i]], "labels": ol[i, : kept[i]]} for i in range(n)]
+
+    @torch.no_grad()
     def render(self, images: List[Tensor], detections: Optional[List[Dict[str, Tensor]]] = None, names: Optional[Sequence[str]] = None, **kw: Any) -> List[Tensor]:
         """The images with their detections drawn in -- outline, label background, "name score" text per box, the first detection on top: the device form of the
         reference's `Detections.render()` (yolort/v5/models/common.py:575-652 -> Annotator.box_label, yolort/v5/utils/plots.py:98-159).  `images`: the list forward()

@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import torch
 from torch import Tensor
@@ -612,3 +612,137 @@ def postprocess_logits_tta(view_outputs: Sequence[Sequence[Tensor]], scales: Seq
         cap = n * (1 << ((cap + n - 1) // n - 1).bit_length())
     counts = pb.count.cpu().tolist()
     return slab_to_list(pb.boxes, pb.scores, pb.labels, counts)
+
+
+class PackedLinear(NamedTuple):
+    """A linear layer as ymi_classify_head reads it: weight (ceil(N / 32) * 32, K) of the compute dtype, K-contiguous, rows >= N zero; fp32 bias padded alike"""
+    weight: Tensor
+    bias: Tensor
+    out_features: int
+    in_features: int
+
+
+def pack_linear(weight: Tensor, bias: Optional[Tensor], dtype: torch.dtype) -> PackedLinear:
+    """nn.Linear's (N, K) weight -- or a 1x1 Conv2d's (N, K, 1, 1) -- and bias packed once for ops.classify_head: one rounding of every weight to `dtype`"""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight.reshape(weight.shape[0], weight.shape[1])
+    if weight.dim() != 2:
+        raise YmiError(f"pack_linear: expected an (N, K) weight or an (N, K, 1, 1) one, got {tuple(weight.shape)}")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise YmiError(f"classify_head computes in float16 or bfloat16 (got {dtype}): the fp32 parity mode has no classifier head")
+    n, k = int(weight.shape[0]), int(weight.shape[1])
+    n_pad = (n + 31) // 32 * 32
+    w = torch.zeros((n_pad, k), device=weight.device, dtype=dtype)
+    w[:n] = weight.detach().to(dtype)
+    b = torch.zeros(n_pad, device=weight.device, dtype=torch.float32)
+    if bias is not None:
+        b[:n] = bias.detach().to(torch.float32)
+    return PackedLinear(w, b, n, k)
+
+
+def _pooled_map(m, dtype: torch.dtype):
+    """a map of classify_head -> (keep-alive, pointer, n, pixels, c, pixel stride): an engine.View, or an NHWC tensor (n, h, w, c) that may be a channel slice"""
+    if isinstance(m, View):
+        if m.dtype != dtype:
+            raise YmiError(f"classify_head: a map of {m.dtype} for a head computing in {dtype}")
+        return m.base, m.ptr, m.n, m.h * m.w, m.c, m.cs
+    if not isinstance(m, Tensor) or m.dim() != 4:
+        raise YmiError("classify_head: a map is an engine.View or an NHWC tensor (n, h, w, c)")
+    if not m.is_cuda:
+        raise YmiError("classify_head runs on an MI355X only (no CPU fallback)")
+    if m.dtype != dtype:
+        raise YmiError(f"classify_head: a map of {m.dtype} for a head computing in {dtype}")
+    n, h, w, c = (int(v) for v in m.shape)
+    cs = m.stride(2) if w > 1 else (m.stride(1) if h > 1 else (m.stride(0) if n > 1 else c))
+    want = (h * w * cs, w * cs, cs, 1)
+    if cs < c or cs % 8 or m.data_ptr() % 16 or any(size > 1 and st != ws for size, st, ws in zip(m.shape, m.stride(), want)):
+        m, cs = m.contiguous(), c
+    return m, m.data_ptr(), n, h * w, c, cs
+
+
+def classify_head(maps, w1, b1: Optional[Tensor] = None, w2=None, b2: Optional[Tensor] = None, *, dtype: torch.dtype = torch.float16, n_split: int = 0,
+                  out: Optional[Tensor] = None, hidden: Optional[Tensor] = None) -> Tensor:
+    """The tail of a classifier on the MI355X (ymi_classify_head, include/yolort_amd.h, where the arithmetic is written out): global average pool of one NHWC map or of
+    up to four (their channels side by side, torch.cat(..., 1)), then Linear -- `Classify`'s head, ONE launch -- or Linear, Hardswish, Linear -- DarkNetV4 / V6's
+    `avgpool` + `classifier` in eval, TWO launches.  maps: engine.Views or NHWC tensors (n, h, w, c) of `dtype` (fp16 / bf16), channel slices of a wider buffer
+    included, c a multiple of 8; w1 / w2: (N, K) weights (an (N, K, 1, 1) conv weight likewise) with biases b1 / b2, or `pack_linear` results (packed once, as the
+    models cache them).  -> fp32 logits (n, N_last) on the device, NO synchronisation.  n_split: see the header (0 = the launcher's rule).  out / hidden: contiguous
+    device buffers to write the logits (n, N_last) fp32 / the hidden activations (n, N) of `dtype` into (allocated when None).  No CPU fallback; fp32 as the compute
+    dtype (the parity mode) is refused."""
+    lib = _lib.load(require_gpu=True)
+    maps = list(maps) if isinstance(maps, (list, tuple)) else [maps]
+    if not 1 <= len(maps) <= _lib.CLASSIFY_MAX_MAPS:
+        raise YmiError(f"classify_head: {len(maps)} maps (1 .. {_lib.CLASSIFY_MAX_MAPS})")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise YmiError(f"classify_head computes in float16 or bfloat16 (got {dtype}): the fp32 parity mode has no classifier head")
+    p1 = w1 if isinstance(w1, PackedLinear) else pack_linear(w1, b1, dtype)
+    p2 = None if w2 is None else (w2 if isinstance(w2, PackedLinear) else pack_linear(w2, b2, dtype))
+    views = [_pooled_map(m, dtype) for m in maps]
+    n = views[0][2]
+    if any(v[2] != n for v in views):
+        raise YmiError(f"classify_head: the maps have {[v[2] for v in views]} rows")
+    if sum(v[4] for v in views) != p1.in_features or (p2 is not None and p2.in_features != p1.out_features):
+        raise YmiError(f"classify_head: {sum(v[4] for v in views)} channels into a ({p1.out_features}, {p1.in_features}) weight" + (f", then ({p2.out_features}, {p2.in_features})" if p2 else ""))
+    if any(p.weight.dtype != dtype or not p.weight.is_cuda for p in (p1, p2) if p is not None):
+        raise YmiError(f"classify_head: the packed weights must be {dtype} tensors on the device")
+    dev = p1.weight.device
+    d = _lib.ClassifyDesc()
+    for i, (_, ptr, _, hw, c, cs) in enumerate(views):
+        d.maps[i], d.hw[i], d.c[i], d.cs[i] = ptr, hw, c, cs
+    d.num_maps, d.n, d.n1, d.dtype, d.n_split = len(views), n, p1.out_features, _lib.dtype_code(dtype), int(n_split)
+    d.w1, d.b1 = p1.weight.data_ptr(), p1.bias.data_ptr()
+    logits = torch.empty((n, (p2 or p1).out_features), device=dev, dtype=torch.float32) if out is None else out
+    if p2 is not None and hidden is None:
+        hidden = torch.empty((n, p1.out_features), device=dev, dtype=dtype)
+    for t, shape, dt in ((logits, (n, (p2 or p1).out_features), torch.float32), (hidden, (n, p1.out_features), dtype)):
+        if t is not None and (not t.is_cuda or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise YmiError(f"classify_head: an output buffer must be a contiguous device tensor of shape {shape} and dtype {dt}")
+    if p2 is not None:
+        d.mode, d.n2, d.w2, d.b2, d.hidden = _lib.CLASSIFY_HIDDEN_LOGITS, p2.out_features, p2.weight.data_ptr(), p2.bias.data_ptr(), hidden.data_ptr()
+    d.logits = logits.data_ptr()
+    check(lib.ymi_classify_head(C.byref(d), _lib.stream_ptr()), "ymi_classify_head")
+    return logits
+
+
+def _raise_filter_status(bits: int) -> None:
+    if bits & _lib.FILTER_STATUS_BAD_COUNT:
+        raise ValueError("second_stage_filter: a count of the slab lies outside [0, K]")
+    if bits & (_lib.FILTER_STATUS_TOTAL | _lib.FILTER_STATUS_CAPACITY):
+        raise ValueError("second_stage_filter: the crops' total disagrees with the slab's counts, or the logits hold fewer rows than the slab has detections")
+
+
+def second_stage_filter(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, logits: Tensor, total: Tensor, *, class_map: Optional[Tensor] = None):
+    """The last line of the reference's apply_classifier (yolort/v5/utils/general.py:721-722) on the slab, on the MI355X in one launch (ymi_second_stage_filter): a
+    detection survives iff the arg-max of its second-stage logits row -- through `class_map` (int32 [nc2], second-stage class -> detector label; None = the identity)
+    -- equals its label.  boxes (n, K, 4), scores (n, K), labels (n, K), counts (n,): the slab; logits (capacity, nc2) fp32 in ops.crop_detections' row order and that
+    call's `total`.  -> (boxes, scores, labels, counts, cls2, status): the filtered slab (same shapes, kept rows in slab order, slots past a new count zero), cls2
+    (n, K) int32 = the second-stage class of every ORIGINAL detection (-1 where there is none) and the int32 status word on the device (_lib.FILTER_STATUS_*;
+    `_raise_filter_status` turns it into an exception once it has been read).  Ties go to the lowest class, a NaN beats every number (torch.argmax on the CPU).
+    NO synchronisation, no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    ins = (boxes, scores, labels, counts, logits, total) + (() if class_map is None else (class_map,))
+    if not all(t.is_cuda for t in ins):
+        raise YmiError("second_stage_filter runs on an MI355X only (no CPU fallback)")
+    n = int(counts.shape[0])
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4 or tuple(scores.shape) != tuple(boxes.shape[:2]) or tuple(labels.shape) != tuple(boxes.shape[:2]) or counts.dim() != 1:
+        raise YmiError(f"second_stage_filter: expected the slab (n, K, 4) / (n, K) / (n, K) / (n,), got {tuple(boxes.shape)} {tuple(scores.shape)} {tuple(labels.shape)} {tuple(counts.shape)}")
+    if logits.dim() != 2 or logits.shape[1] < 1 or total.numel() < 1 or (class_map is not None and tuple(class_map.shape) != (logits.shape[1],)):
+        raise YmiError(f"second_stage_filter: expected logits (capacity, nc2), total [2] and class_map (nc2,), got {tuple(logits.shape)} {tuple(total.shape)}")
+    k, dev = int(boxes.shape[1]), boxes.device
+    b = boxes.detach().to(torch.float32).contiguous()
+    s = scores.detach().to(torch.float32).contiguous()
+    l = labels.detach().to(torch.int64).contiguous()
+    c = counts.detach().to(torch.int32).contiguous()
+    lg = logits.detach().to(torch.float32).contiguous()
+    tt = total.detach().to(torch.int32).contiguous()
+    cm = None if class_map is None else class_map.detach().to(torch.int32).contiguous()
+    ob, os_, ol, oc = torch.empty_like(b), torch.empty_like(s), torch.empty_like(l), torch.empty_like(c)
+    cls2 = torch.empty((n, k), device=dev, dtype=torch.int32)
+    status = torch.empty(1, device=dev, dtype=torch.int32)
+    d = _lib.FilterDesc()
+    d.boxes, d.scores, d.labels, d.counts, d.logits, d.total = b.data_ptr(), s.data_ptr(), l.data_ptr(), c.data_ptr(), lg.data_ptr(), tt.data_ptr()
+    d.class_map = None if cm is None else cm.data_ptr()
+    d.out_boxes, d.out_scores, d.out_labels, d.out_counts, d.cls2, d.status = ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), oc.data_ptr(), cls2.data_ptr(), status.data_ptr()
+    d.n, d.k, d.cap, d.nc2 = n, k, int(lg.shape[0]), int(lg.shape[1])
+    check(lib.ymi_second_stage_filter(C.byref(d), _lib.stream_ptr()), "ymi_second_stage_filter")
+    return ob, os_, ol, oc, cls2, status

@@ -18,7 +18,7 @@ from ..._lib import ACT_HARDSWISH, ACT_LEAKY, ACT_NONE, ACT_SILU, YmiError
 from ...engine import PackedConv, Plan, View
 from ...hipmodule import HipModule
 
-__all__ = ["Conv", "Bottleneck", "BottleneckCSP", "C3", "SPP", "SPPF", "Focus", "autopad", "focus_transform", "space_to_depth"]
+__all__ = ["Conv", "Bottleneck", "BottleneckCSP", "C3", "SPP", "SPPF", "Focus", "Classify", "autopad", "focus_transform", "space_to_depth"]
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03  # set after construction by the reference (darknetv6.py:110-112)
 
@@ -369,3 +369,43 @@ class SPPF(SPP):
             raise NotImplementedError("the fused pool pyramid implements SPPF(k=5)")
         super().__init__(c1, c2, (5, 9, 13), version=version)
         self.m = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
+
+
+class Classify(nn.Module):
+    """Classification head, (b, c1, h, w) or a list of up to four such maps -> (b, c2) logits (reference :679-689: AdaptiveAvgPool2d(1) per map, torch.cat(..., 1), a
+    1x1 Conv2d with bias, Flatten), as ONE launch of ops.classify_head: the maps are pooled straight into the GEMM's LDS block.  Same parameters as the reference's
+    (`conv.weight`, `conv.bias`).  Limits: k = 1, s = 1, g = 1 (a pooled map is one pixel, so any other kernel is a different layer, and groups are not implemented);
+    every map's channel count a multiple of 8; fp16 / bf16 compute (fp32-parameter modules compute in fp16 unless `compute_dtype` says bf16)."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1):
+        super().__init__()
+        if (k, s, g) != (1, 1, 1):
+            raise NotImplementedError(f"Classify implements k = 1, s = 1, g = 1 only (got k = {k}, s = {s}, g = {g}): the pooled map is one pixel and grouped heads are out of scope")
+        self.aap = nn.AdaptiveAvgPool2d(1)
+        self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g)
+        self.flat = nn.Flatten()
+
+    def forward(self, x):
+        from ... import ops
+        from ...hipmodule import compute_dtype_of, nchw_to_view, weights_signature
+        if self.training:
+            raise NotImplementedError("yolort_amd implements the inference path only; call .eval() (training is out of scope)")
+        xs = list(x) if isinstance(x, (list, tuple)) else [x]
+        if not 1 <= len(xs) <= 4:
+            raise YmiError(f"Classify takes one map or a list of up to four, got {len(xs)}")
+        for t in xs:
+            if not t.is_cuda:
+                raise YmiError("yolort_amd runs on an MI355X only: move the model and inputs to 'cuda' (there is no CPU fallback)")
+            if t.dim() != 4 or t.shape[1] % 8:
+                raise YmiError(f"Classify expects NCHW maps whose channel count is a multiple of 8, got shape {tuple(t.shape)}")
+        cdt = compute_dtype_of(self)
+        if cdt == torch.float32:
+            raise YmiError("the classifier head computes in float16 or bfloat16: compute_dtype = torch.float32 (the parity mode) has no head")
+        with torch.cuda.device(xs[0].device):
+            key = (cdt, xs[0].device.index, weights_signature(self))
+            cached = self.__dict__.get("_ymi_head")
+            if cached is None or cached[0] != key:
+                cached = self.__dict__["_ymi_head"] = (key, ops.pack_linear(self.conv.weight, self.conv.bias, cdt))
+            views = [nchw_to_view(None, t, t.shape[1], dtype=cdt) for t in xs]
+            logits = ops.classify_head(views, cached[1], dtype=cdt)
+        return logits.to(xs[0].dtype if xs[0].dtype.is_floating_point else torch.float32)
