@@ -550,6 +550,41 @@ int ymi_copy_view(const void* x, int x_cstride, int npix, int c, void* y, int y_
                   void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depthwise convolution: y = act(dwconv(x, W) + bias) (+ res), groups = channels, channel multiplier 1.  Replaces the conv2d(groups=c) -> BatchNorm2d -> act of
+ * DWConv (yolort/v5/models/common.py:76-91) and of GhostConv.cv2 (:386-396), with BatchNorm folded into W / bias on the host like ymi_conv2d's.
+ *   x        NHWC view (n, h, w_in, c), pixel stride x_cstride;  y  NHWC view (n, ho, wo, c), pixel stride y_cstride;  res  optional view of y's shape, pixel stride
+ *            res_cstride (NULL = none).  The three strides are independent (each >= c, a multiple of 8): channel slices of wider buffers are valid views.
+ *   w        packed [k * k][c] of `dtype`, tap index ky * k + kx;  bias  fp32 [c]
+ *   k in {3, 5}, s in {1, 2}, p = k / 2, ho = (h + 2 p - k) / s + 1 (wo likewise);  c % 8 == 0;  dtype YMI_F16 / YMI_BF16 (compute and output);  every pointer 16-byte
+ *   aligned;  act YMI_ACT_NONE / SILU / HARDSWISH / LEAKY (the epilogue functions of the other kernels: SiLU as ymi_conv2d's, the other two as ymi_act's).
+ * THE ARITHMETIC (the contract): the product of two 16-bit operands is taken in fp32, where it is exact; the k * k products of an output are summed in fp32 in raster
+ * tap order (ky outer, kx inner) starting from +0; out-of-image taps are skipped (the kernel adds x = 0, which is the same for finite weights); then + the fp32
+ * bias, the activation in fp32, + the residual in fp32 (AFTER the activation, as ymi_conv2d), and ONE round-to-nearest-even to `dtype`.  No fp16 accumulation, no
+ * packed-half math, no matrix instructions (the reduction is per channel).
+ * dwconv_kernel (csrc/dwconv.hip): a workgroup of 256 threads owns YMI_DWCONV_TILE_H x YMI_DWCONV_TILE_W_S<s> output pixels x 64 channels, grid (tiles, slabs of 64
+ * channels, images); the input halo tile and the slab's weights are staged in LDS with 16-byte loads (zeros outside the image), a thread owns 8 channels of a short
+ * vertical run of outputs and reuses each input row across the run's windows.  Nothing outside y's (n, ho, wo, c) elements is written, nothing outside x's and res's
+ * (.., c) elements is read.  YMI_EINVAL (nothing is launched): a null x / w / bias / y, c % 8 != 0, k / s / p outside the sets, a dtype other than F16 / BF16, a stride
+ * below c or not a multiple of 8, a misaligned pointer, ho / wo that do not follow from h / w_in, n > 65535.  No allocation, no synchronisation: ordered on
+ * `stream`, may be captured.  ABI stays 6: one new struct, two new functions.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_DWCONV_TILE_H 8
+#define YMI_DWCONV_TILE_W_S1 16 /* output tile of a workgroup: 8 x 16 at stride 1 */
+#define YMI_DWCONV_TILE_W_S2 8  /* 8 x 8 at stride 2 */
+typedef struct ymi_dwconv_desc {
+    const void* x;
+    const void* w;
+    const float* bias;
+    void* y;
+    const void* res;
+    int32_t n, h, w_in, c, x_cstride, y_cstride, res_cstride;
+    int32_t ho, wo;
+    int32_t k, s, p;
+    int32_t act, dtype;
+} ymi_dwconv_desc;
+int ymi_dwconv2d(const ymi_dwconv_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-process (yolort/models/box_head.py:328-360,414-427 + torchvision batched_nms).
  * ymi_postprocess runs, on `stream`, with no host sync:
  *   1. decode   sigmoid, xy=(s*2-0.5+grid)*stride, wh=(s*2)^2*anchor (yolort/models/_utils.py:59-60,
@@ -862,6 +897,9 @@ int ymi_plan_add_post_finish(ymi_plan* p, const ymi_post_desc* d);
  * ymi_plan_set_classes writes that workspace's mask once, and an exported plan carries both descriptors) */
 int ymi_plan_add_scale_view(ymi_plan* p, const void* src, int n, int h, int w, void* dst, int dh, int dw, int sh, int sw, int flip, int dtype);
 int ymi_plan_add_post_decode_view(ymi_plan* p, const ymi_post_desc* sink, const ymi_post_view* view);
+/* ymi_dwconv2d as a plan op: the descriptor is checked here (YMI_EINVAL as the direct call), replays under graph capture, is timed by ymi_plan_profile and travels with
+ * an exported plan (it is kept in the op record's convolution descriptor: the record's size, which a plan file pins, is unchanged) */
+int ymi_plan_add_dwconv(ymi_plan* p, const ymi_dwconv_desc* d);
 int ymi_plan_num_ops(const ymi_plan* p);
 /* ymi_post_set_classes for every post-process descriptor recorded in the plan that carries YMI_POST_CLASS_FILTER (YMI_EINVAL if none does).  The plan remembers the
  * list: ymi_plan_export stores it, and ymi_plan_import writes the masks again before it returns, so an imported plan filters as the exporting one did; the consumer

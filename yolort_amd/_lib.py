@@ -214,6 +214,17 @@ class FilterDesc(C.Structure):
     ]
 
 
+class DwConvDesc(C.Structure):
+    """ymi_dwconv_desc: the views, packed [k * k][c] weights, fp32 bias and geometry of one depthwise convolution (ymi_dwconv2d)"""
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("res", C.c_void_p),
+        ("n", C.c_int32), ("h", C.c_int32), ("w_in", C.c_int32), ("c", C.c_int32), ("x_cstride", C.c_int32), ("y_cstride", C.c_int32), ("res_cstride", C.c_int32),
+        ("ho", C.c_int32), ("wo", C.c_int32), ("k", C.c_int32), ("s", C.c_int32), ("p", C.c_int32), ("act", C.c_int32), ("dtype", C.c_int32),
+    ]
+
+
+DWCONV_TILE = {1: (8, 16), 2: (8, 8)}   # YMI_DWCONV_TILE_H x YMI_DWCONV_TILE_W_S<stride>: the output tile of a workgroup
+
 CLASSIFY_MAX_MAPS, CLASSIFY_MAX_K, CLASSIFY_LOGITS, CLASSIFY_HIDDEN_LOGITS = 4, 2496, 0, 1   # YMI_CLASSIFY_*
 FILTER_STATUS_BAD_COUNT, FILTER_STATUS_TOTAL, FILTER_STATUS_CAPACITY, FILTER_MAX_K = 1, 2, 4, 32768   # YMI_FILTER_*
 
@@ -297,6 +308,8 @@ _SIGS = {
     "ymi_crop_resize_nv12": (C.c_int, [C.POINTER(CropNv12Desc), C.c_void_p]),
     "ymi_classify_head": (C.c_int, [C.POINTER(ClassifyDesc), C.c_void_p]),
     "ymi_second_stage_filter": (C.c_int, [C.POINTER(FilterDesc), C.c_void_p]),
+    "ymi_dwconv2d": (C.c_int, [C.POINTER(DwConvDesc), C.c_void_p]),
+    "ymi_plan_add_dwconv": (C.c_int, [C.c_void_p, C.POINTER(DwConvDesc)]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

@@ -62,8 +62,10 @@ int post_set_classes_launch(const ymi_post_desc* d, const int32_t* classes, int 
 int conv_head_decode_launch(const ymi_conv_desc* d, const ymi_post_desc* post, int level, hipStream_t s);
 int conv_head_decode_group_launch(const ymi_conv_desc* descs, int n_levels, const ymi_post_desc* post, hipStream_t s);
 int post_decode_view_launch(const ymi_post_desc* d, const ymi_post_view* v, hipStream_t s);
+int dwconv_check(const ymi_dwconv_desc* d);
+int dwconv_launch(const ymi_dwconv_desc* d, hipStream_t s);
 
-enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW };
+enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW, OP_DWCONV };
 
 struct Op {
     OpKind kind;
@@ -77,6 +79,16 @@ struct Op {
     int i[8];
     ymi_post_view view;   // OP_POST_VIEW: one view of augmented inference (its sink is `post`)
 };
+
+// OP_DWCONV keeps its descriptor in the fields of the same name of op.conv (cin = c, kh = k, sh = s, ph = p): the record does not grow -- a plan file pins
+// sizeof(Op) -- and the five pointers are relocated by ymi_plan_export / ymi_plan_import like a convolution's
+static ymi_dwconv_desc dwconv_of(const ymi_conv_desc& c) {
+    ymi_dwconv_desc d;
+    d.x = c.x; d.w = c.w; d.bias = c.bias; d.y = c.y; d.res = c.res;
+    d.n = c.n; d.h = c.h; d.w_in = c.w_in; d.c = c.cin; d.x_cstride = c.x_cstride; d.y_cstride = c.y_cstride; d.res_cstride = c.res_cstride;
+    d.ho = c.ho; d.wo = c.wo; d.k = c.kh; d.s = c.sh; d.p = c.ph; d.act = c.act; d.dtype = c.dtype;
+    return d;
+}
 
 static int run_op(const Op& op, hipStream_t s) {
     switch (op.kind) {
@@ -93,6 +105,10 @@ static int run_op(const Op& op, hipStream_t s) {
         case OP_ACT: return ymi_act(op.y, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.x, op.i[5], s);
         case OP_SCALE_VIEW: return ymi_scale_view(op.x, op.i[0], op.i[1], op.i[2], op.y, op.i[3], op.i[4], op.i[5], op.i[6], op.i[7] & 1, op.i[7] >> 1, s);
         case OP_POST_VIEW: return post_decode_view_launch(&op.post, &op.view, s);
+        case OP_DWCONV: {
+            const ymi_dwconv_desc d = dwconv_of(op.conv);
+            return dwconv_launch(&d, s);
+        }
     }
     set_error("unknown op kind");
     return YMI_EINVAL;
@@ -323,6 +339,21 @@ extern "C" int ymi_plan_add_post_decode_view(ymi_plan* p, const ymi_post_desc* s
     op.kind = OP_POST_VIEW;
     op.post = *sink;
     op.view = *view;
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
+extern "C" int ymi_plan_add_dwconv(ymi_plan* p, const ymi_dwconv_desc* d) {
+    YMI_REQUIRE(p && d, "ymi_plan_add_dwconv: null argument");
+    if (const int rc = dwconv_check(d)) return rc;
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_DWCONV;
+    ymi_conv_desc& c = op.conv;
+    c.x = d->x; c.w = d->w; c.bias = d->bias; c.y = d->y; c.res = d->res;
+    c.n = d->n; c.h = d->h; c.w_in = d->w_in; c.cin = d->c; c.x_cstride = d->x_cstride; c.y_cstride = d->y_cstride; c.res_cstride = d->res_cstride;
+    c.ho = d->ho; c.wo = d->wo; c.kh = d->k; c.sh = d->s; c.ph = d->p; c.act = d->act; c.dtype = d->dtype;
     p->ops.push_back(op);
     drop_graph(p);
     return (int)p->ops.size() - 1;

@@ -112,6 +112,12 @@ __device__ __forceinline__ float from16(uint16_t v) {
     else return bf2f(v);
 }
 
+// Hardswish / LeakyReLU(0.1) in fp32, torch's own order of operations (act_kernel of preproc_pool.hip and the depthwise epilogue of dwconv.hip)
+__device__ __forceinline__ float act_legacy_f32(float v, int act) {
+    if (act == YMI_ACT_HARDSWISH) return (v * fminf(fmaxf(v + 3.0f, 0.0f), 6.0f)) / 6.0f;
+    return v > 0.0f ? v : v * 0.1f;
+}
+
 // element index of channel c at (y, x) of an h x w image: planar (3, h, w), or interleaved (h, w, 3) for YMI_U8_HWC
 template <int DT>
 __device__ __forceinline__ int64_t src_index(int c, int y, int x, int w, int64_t plane) {

@@ -768,11 +768,8 @@ __global__ __launch_bounds__(256) void copy_view_kernel(const uint16_t* x, int x
 // AFTER the activation like the reference does.  The convolution epilogues carry SiLU / identity only: folding these two into the general epilogue of every conv kernel
 // moved the register allocation of kernels that sat at their limit (the 256-wide 8-wave implicit GEMM: 2-3 x slower on the r6.0 plans, profiles/r05k_*), so an r3.1
 // convolution runs with YMI_ACT_NONE and this kernel rewrites its output in place: one 16-byte packet (8 halves / 4 floats) per thread, HBM-bound.
-// fp32 mode: torch's own order of operations -- (x * min(max(x + 3, 0), 6)) / 6 with a true division; x > 0 ? x : 0.1 x -- on the exactly stored fp32 pre-activation.
-__device__ __forceinline__ float act_legacy_f32(float v, int act) {
-    if (act == YMI_ACT_HARDSWISH) return (v * fminf(fmaxf(v + 3.0f, 0.0f), 6.0f)) / 6.0f;
-    return v > 0.0f ? v : v * 0.1f;
-}
+// fp32 mode: torch's own order of operations -- (x * min(max(x + 3, 0), 6)) / 6 with a true division; x > 0 ? x : 0.1 x -- on the exactly stored fp32 pre-activation
+// (act_legacy_f32, common.hpp: the depthwise kernel's epilogue shares it).
 
 template <int DT>
 __global__ __launch_bounds__(256) void act_kernel(uint16_t* y, int y_cs, int64_t npix, int c, int act, const uint16_t* res, int res_cs) {

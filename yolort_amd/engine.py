@@ -118,6 +118,27 @@ class PackedConv:
         return t
 
 
+class PackedDWConv:
+    """Weights of one depthwise convolution (groups = channels, multiplier 1), BatchNorm folded with PackedConv's formula, packed [k*k][c] of the compute dtype
+    (tap index ky * k + kx) for csrc/dwconv.hip, plus the fp32 bias."""
+
+    def __init__(self, weight: Tensor, bias: Optional[Tensor], bn: Optional[Tuple[Tensor, Tensor, Tensor, Tensor, float]], dtype: torch.dtype, device: torch.device):
+        w = weight.detach().to(device=device, dtype=torch.float32)
+        c, one, kh, kw = w.shape
+        if one != 1 or kh != kw:
+            raise YmiError(f"depthwise weights must be (c, 1, k, k), got {tuple(w.shape)}")
+        b = torch.zeros(c, device=device, dtype=torch.float32) if bias is None else bias.detach().to(device=device, dtype=torch.float32)
+        if bn is not None:
+            g, beta, mean, var, eps = bn
+            scale = g.detach().to(device=device, dtype=torch.float32) / torch.sqrt(var.detach().to(device=device, dtype=torch.float32) + eps)
+            w = w * scale.view(-1, 1, 1, 1)
+            b = beta.detach().to(device=device, dtype=torch.float32) + (b - mean.detach().to(device=device, dtype=torch.float32)) * scale
+        self.c, self.k, self.dtype = c, kh, dtype
+        self.w = w.reshape(c, kh * kw).t().contiguous().to(dtype)
+        self.bias = b.contiguous()
+        self._ktabs: Dict[Tuple[int, int], Tensor] = {}   # (none: Plan.export walks packed weights of both kinds alike)
+
+
 _TILE_TABLE: Optional[Dict[str, int]] = None
 TILE_TABLE_PATH = os.environ.get("YOLORT_AMD_TILE_TABLE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "tiles_gfx950.json")   # override: A/B runs only
 
@@ -375,6 +396,33 @@ class Plan:
                      bytes=float(ref_reads * x.n * x.h * x.w * cin_real * esz + x.n * ho * wo * pc.cout * out.base.element_size() + pc.cout * pc.k_real * esz) + chain_bytes,
                      ref_convs=ref_reads + (1 if chain is not None else 0), tile=int(d.tile),
                      shape=f"{x.c}->{pc.cout} k{pc.kh}x{pc.kw} s{s[0]} {x.h}x{x.w}->{ho}x{wo}")
+        return out
+
+    def dwconv(self, x: View, pd: PackedDWConv, k: int, stride: int = 1, act: int = ACT_SILU, out: Optional[View] = None, res: Optional[View] = None,
+               name: str = "dwconv") -> View:
+        """y = act(dwconv(x, W) + bias) (+ res): the depthwise kernel (ymi_dwconv2d, csrc/dwconv.hip), k in {3, 5}, stride 1 / 2, pad k // 2; all four activation
+        codes ride in its epilogue.  `x`, `out` and `res` may be channel slices of wider buffers."""
+        if self.fp32:
+            raise YmiError(f"{name}: the fp32 parity mode has no depthwise kernel (compute in float16 or bfloat16)")
+        if x.c != pd.c or k != pd.k:
+            raise YmiError(f"{name}: input view has {x.c} channels / k = {k}, packed depthwise weights expect {pd.c} / k = {pd.k}")
+        ho, wo = conv_out_hw(x.h, x.w, (k, k), (stride, stride), (k // 2, k // 2))
+        if out is None:
+            out = self.alloc(x.n, ho, wo, pd.c)
+        if (out.n, out.h, out.w, out.c) != (x.n, ho, wo, pd.c):
+            raise YmiError(f"{name}: output view {(out.n, out.h, out.w, out.c)} != expected {(x.n, ho, wo, pd.c)}")
+        if res is not None and (res.n, res.h, res.w, res.c) != (out.n, out.h, out.w, out.c):
+            raise YmiError(f"{name}: shortcut view does not match the output")
+        d = _lib.DwConvDesc()
+        d.x, d.w, d.bias, d.y, d.res = x.ptr, pd.w.data_ptr(), pd.bias.data_ptr(), out.ptr, None if res is None else res.ptr
+        d.n, d.h, d.w_in, d.c, d.x_cstride, d.y_cstride, d.res_cstride = x.n, x.h, x.w, pd.c, x.cs, out.cs, 0 if res is None else res.cs
+        d.ho, d.wo, d.k, d.s, d.p, d.act, d.dtype = ho, wo, k, stride, k // 2, act, dtype_code(pd.dtype)
+        self.keep.extend([pd, d])
+        self.io[self.num_ops] = {"name": name, "x": x, "y": out, "res": res, "stride": (stride, stride), "pad": (k // 2, k // 2)}
+        esz = out.base.element_size()
+        self._record(self.lib.ymi_plan_add_dwconv(self.handle, C.byref(d)), name, kind="dwconv", flops=2.0 * x.n * ho * wo * pd.c * k * k,
+                     bytes=float((x.n * x.h * x.w + x.n * ho * wo * (2 if res is not None else 1)) * pd.c * esz + k * k * pd.c * esz),
+                     shape=f"dw{pd.c} k{k}x{k} s{stride} {x.h}x{x.w}->{ho}x{wo}")
         return out
 
     def _pinned_ok(self, d: ConvDesc, tile: int) -> bool:
@@ -835,7 +883,7 @@ class Plan:
         def walk(o):
             if isinstance(o, Tensor):
                 add(o, REGION_SCRATCH)
-            elif isinstance(o, PackedConv):
+            elif isinstance(o, (PackedConv, PackedDWConv)):
                 add(o.w, REGION_CONST)
                 add(o.bias, REGION_CONST)
                 for kt in o._ktabs.values():

@@ -1,12 +1,14 @@
 """YOLOv5 building blocks (r3.1 / r4.0 / r6.0 forms) as HIP plan emitters.
 
 Same constructor signatures, attribute names and state_dict keys as the reference's blocks
-(yolort/v5/models/common.py: Conv :42, Bottleneck :94, BottleneckCSP :119, C3 :149, SPP :176, SPPF :190, Focus :210) so that its
+(yolort/v5/models/common.py: Conv :42, DWConv :76, Bottleneck :94, BottleneckCSP :119, C3 :149, SPP :176, SPPF :190, Focus :210, C3Ghost :378, GhostConv :386,
+GhostBottleneck :399) so that its
 checkpoints load unchanged; the arithmetic is the fused implicit-GEMM kernel (csrc/conv_igemm.hip)
-instead of conv2d -> BatchNorm2d -> SiLU -> cat.
+instead of conv2d -> BatchNorm2d -> SiLU -> cat, and the depthwise kernel (csrc/dwconv.hip) for the convolutions with groups == channels.
 """
 from __future__ import annotations
 
+import math
 import os
 
 from typing import Dict, Optional, Tuple
@@ -15,10 +17,11 @@ import torch
 from torch import nn
 
 from ..._lib import ACT_HARDSWISH, ACT_LEAKY, ACT_NONE, ACT_SILU, YmiError
-from ...engine import PackedConv, Plan, View
+from ...engine import PackedConv, PackedDWConv, Plan, View
 from ...hipmodule import HipModule
 
-__all__ = ["Conv", "Bottleneck", "BottleneckCSP", "C3", "SPP", "SPPF", "Focus", "Classify", "autopad", "focus_transform", "space_to_depth"]
+__all__ = ["Conv", "DWConv", "Bottleneck", "BottleneckCSP", "C3", "C3Ghost", "GhostConv", "GhostBottleneck", "SPP", "SPPF", "Focus", "Classify", "autopad", "focus_transform",
+           "space_to_depth"]
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03  # set after construction by the reference (darknetv6.py:110-112)
 
@@ -44,12 +47,15 @@ def act_code(act: nn.Module) -> int:
 
 
 class Conv(HipModule):
-    """conv2d (no bias) + BatchNorm2d + SiLU (r4.0 / r6.0) or Hardswish (r3.1), fused (reference common.py:42-73)."""
+    """conv2d (no bias) + BatchNorm2d + SiLU (r4.0 / r6.0) or Hardswish (r3.1), fused (reference common.py:42-73).  g == c1 == c2 is the depthwise form
+    (csrc/dwconv.hip: k in {3, 5}, s in {1, 2}, 'same' padding, every activation in its epilogue); any other g != 1 is not implemented."""
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, act=True, version="r4.0"):
         super().__init__()
-        if g != 1:
+        if g != 1 and not (g == c1 == c2):
             raise NotImplementedError("grouped convolutions are not on the YOLOv5 hot path")
+        if g != 1 and (k not in (3, 5) or s not in (1, 2) or autopad(k, p) != k // 2):
+            raise NotImplementedError(f"the depthwise kernel implements k in {{3, 5}}, s in {{1, 2}} and padding k // 2 (got k = {k}, s = {s}, p = {p})")
         if version not in ("r4.0", "r3.1"):
             raise NotImplementedError(f"Currently doesn't support version {version}.")
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g, bias=False)
@@ -65,7 +71,11 @@ class Conv(HipModule):
     def _input_cpad(self, c: int) -> int:
         return 4 if self._is_stem() else (c + 7) // 8 * 8
 
-    def packed(self, dtype: torch.dtype, device: torch.device, cin_view: int) -> PackedConv:
+    @property
+    def depthwise(self) -> bool:
+        return self.conv.groups != 1
+
+    def packed(self, dtype: torch.dtype, device: torch.device, cin_view: int):
         sig = tuple(t._version for t in (self.conv.weight, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var)) + (self.conv.weight.data_ptr(),)
         stem = cin_view == 4 and self._is_stem()
         key = (dtype, device, cin_view, stem)
@@ -73,14 +83,80 @@ class Conv(HipModule):
         if hit is not None and hit[0] == sig:
             return hit[1]
         bn = (self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, float(self.bn.eps))
-        pc = PackedConv(self.conv.weight, None, bn, dtype, device, cin_pad=None if stem else cin_view, stem_superpixel=stem)
+        pc = PackedDWConv(self.conv.weight, None, bn, dtype, device) if self.depthwise else PackedConv(self.conv.weight, None, bn, dtype, device, cin_pad=None if stem else cin_view, stem_superpixel=stem)
         self._packed[key] = (sig, pc)
         return pc
 
     def emit(self, plan: Plan, x: View, out: Optional[View] = None, res: Optional[View] = None, name: str = "conv", up2_out: Optional[View] = None,
              chain=None) -> View:
         pc = self.packed(plan.dtype, plan.device, x.c)
+        if self.depthwise:
+            if up2_out is not None or chain is not None:
+                raise YmiError(f"{name}: a depthwise convolution carries no folded upsample and no chained convolution")
+            return plan.dwconv(x, pc, self.conv.kernel_size[0], self.conv.stride[0], act_code(self.act), out=out, res=res, name=name)
         return plan.conv(x, pc, self.conv.stride, self.conv.padding, act_code(self.act), out=out, res=res, name=name, up2_out=up2_out, chain=chain)
+
+
+class DWConv(Conv):
+    """Depthwise Conv (reference common.py:76-91: groups = gcd(c1, c2)).  Implemented where c1 == c2 (pure depthwise, no channel multiplier) and k is 3 or 5."""
+
+    def __init__(self, c1, c2, k=1, s=1, act=True, version="r4.0"):
+        if c1 != c2 or k not in (3, 5):
+            raise NotImplementedError(f"DWConv is implemented for c1 == c2 (no channel multiplier, no partial groups) and k in {{3, 5}}, got c1 = {c1}, c2 = {c2}, k = {k}")
+        super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), act=act, version=version)
+
+
+class GhostConv(HipModule):
+    """cat(cv1(x), cv2(cv1(x))), cv2 a depthwise 5 x 5 (reference common.py:386-396).  No concat kernel: cv1 writes channels [0, c_) of the c2-channel output, the
+    depthwise launch reads that slice (pixel stride c2) and writes [c_, 2 c_).  Two launches.
+    `res` (GhostBottleneck's sum): the depthwise half takes its half of the shortcut in its epilogue.  The first half is both the depthwise convolution's input
+    (without the shortcut, read as halo by other workgroups) and the block's output (with it), so it cannot be updated by that launch: a third launch runs cv1 again
+    with the shortcut in ITS epilogue and overwrites the half -- the traffic of an in-place add (read c_, read c_, write c_ channels), one rounding instead of two."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act)
+
+    def emit(self, plan: Plan, x: View, out: Optional[View] = None, res: Optional[View] = None, name: str = "ghostconv") -> View:
+        c_ = self.cv1.conv.out_channels
+        if c_ % 8:
+            raise YmiError(f"{name}: GhostConv's half width {c_} must be a multiple of 8")
+        if out is None:
+            k, s, p = self.cv1.conv.kernel_size[0], self.cv1.conv.stride[0], self.cv1.conv.padding[0]
+            out = plan.alloc(x.n, (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1, 2 * c_)
+        if out.c != 2 * c_ or (res is not None and res.c != 2 * c_):
+            raise YmiError(f"{name}: output / shortcut views must have {2 * c_} channels")
+        y = self.cv1.emit(plan, x, out=out.slice_c(0, c_), name=name + ".cv1")
+        self.cv2.emit(plan, y, out=out.slice_c(c_, c_), res=None if res is None else res.slice_c(c_, c_), name=name + ".cv2")
+        if res is not None:
+            self.cv1.emit(plan, x, out=out.slice_c(0, c_), res=res.slice_c(0, c_), name=name + ".cv1+res")
+        return out
+
+
+class GhostBottleneck(HipModule):
+    """conv(x) + shortcut(x) (reference common.py:399-416), conv = GhostConv, (DWConv s2), GhostConv without activation.  The sum costs no pass over the whole output:
+    it rides in the last GhostConv's epilogues (see GhostConv.emit).  Launches: s == 1 (shortcut = x, needs c1 == c2): 2 + 3 = 5;  s == 2: the shortcut branch first
+    (DWConv s2, 1x1 Conv: 2), then 2 + 1 + 3: 8 in all."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1), DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(), GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+    def emit(self, plan: Plan, x: View, out: Optional[View] = None, name: str = "ghostbottleneck") -> View:
+        if isinstance(self.shortcut, nn.Identity):
+            if x.c != 2 * self.conv[2].cv1.conv.out_channels:
+                raise YmiError(f"{name}: the identity shortcut needs c1 == c2")
+            res = x
+        else:
+            res = self.shortcut[1].emit(plan, self.shortcut[0].emit(plan, x, name=name + ".shortcut.0"), name=name + ".shortcut.1")
+        y = self.conv[0].emit(plan, x, name=name + ".conv.0")
+        if not isinstance(self.conv[1], nn.Identity):
+            y = self.conv[1].emit(plan, y, name=name + ".conv.1")
+        return self.conv[2].emit(plan, y, out=out, res=res, name=name + ".conv.2")
 
 
 class Bottleneck(HipModule):
@@ -231,6 +307,16 @@ class C3(HipModule):
         if chain3 is not None:
             return chain3[1]
         return self.cv3.emit(plan, cat, out=out, name=name + ".cv3")
+
+
+class C3Ghost(C3):
+    """C3 whose `m` holds GhostBottlenecks (reference common.py:378-383).  C3.emit's fused, strip and chained forms test isinstance(..., Bottleneck), so it takes the
+    general path: cv1 + cv2 in one launch, every GhostBottleneck through its own emit, the last one writing into the concat half, cv3."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[GhostBottleneck(c_, c_) for _ in range(n)])
 
 
 class BottleneckCSP(HipModule):
