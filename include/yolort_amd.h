@@ -585,6 +585,42 @@ typedef struct ymi_dwconv_desc {
 int ymi_dwconv2d(const ymi_dwconv_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-head self-attention over the pixels of a feature map: the nn.MultiheadAttention core of TransformerLayer (yolort/v5/models/common.py:308-331) without its
+ * projections, which are 1 x 1 convolutions (ymi_conv2d).
+ *     O[n, i, h*d:(h+1)*d] = softmax_j(scale * Q[n, i, h] . K[n, j, h]) @ V[n, j, h]      i, j in [0, S), h in [0, heads)
+ *   q, k, v, o  NHWC views (n, S, c) with c = heads * d: S = H * W pixels in raster order (the token order of x.flatten(2)), head h in channels [h d, (h + 1) d).  Each
+ *               view has its own pixel stride in elements (>= c, a multiple of 8): q, k, v are normally three channel slices of one 3c-channel buffer written by one
+ *               convolution, o may be a channel slice of a wider buffer.  Pointers 16-byte aligned.
+ *   LIMITS      dtype YMI_F16 / YMI_BF16 (operands and output); d in {32, 64, 128}; any S >= 1; n * heads * ceil(S / YMI_ATTN_TILE_Q) < 2^31.  No mask, no dropout,
+ *               keys and queries from the same map (k / v of another length are not expressible).  `scale` is any finite float (the blocks pass d ** -0.5).
+ * THE ARITHMETIC (the contract): both products on the 32x32x16 matrix instruction with fp32 accumulation of exact 16-bit products.  The scores are multiplied by
+ * `scale` in fp32; the soft-max runs in fp32 in the running-maximum / running-sum form over chunks of YMI_ATTN_TILE_K keys: the maximum is subtracted before the
+ * exponential, keys j >= S get the weight 0.0f exactly.  The weights are rounded to `dtype` in registers as the operand of the second product; THE ROW SUM IS TAKEN FROM
+ * THE UNROUNDED fp32 WEIGHTS.  Outputs accumulate in fp32; one fp32 division by the row sum, then ONE round-to-nearest-even to `dtype`.  Hence per element
+ * |o - exact| <= 2 u max_j |v| + u |exact| up to fp32 effects, u = 2^-11 (fp16) / 2^-8 (bf16).
+ * attention_kernel (csrc/attention.hip): ONE launch, no S x S matrix in memory; a workgroup of 2 waves owns (image, head, YMI_ATTN_TILE_Q queries), keeps its Q
+ * fragments in registers and streams K and V of the head through LDS in chunks whose 16-byte global loads run a chunk ahead.  Nothing outside o's (n, S, c) elements is
+ * written (queries i >= S of the last tile are not stored), nothing outside the (.., c) elements of q, k, v is read.  No atomics, no allocation, no synchronisation:
+ * ordered on `stream`, may be captured.
+ * YMI_EINVAL (nothing is launched; the message names ymi_attention): a null descriptor or q / k / v / o, a dtype other than F16 / BF16, d outside {32, 64, 128},
+ * heads < 1 or c != heads * d, S < 1 or n < 0, a pixel stride below c or not a multiple of 8, a misaligned pointer, a scale that is not finite, a grid that does not
+ * fit 31 bits.  n == 0 is a no-op.  ABI stays 6: one new struct, two new functions.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_ATTN_TILE_Q 64 /* queries per workgroup */
+#define YMI_ATTN_TILE_K 64 /* keys per LDS chunk */
+typedef struct ymi_attn_desc {
+    const void* q;
+    const void* k;
+    const void* v;
+    void* o;
+    int32_t n, S, heads, d, c;
+    int32_t q_cstride, k_cstride, v_cstride, o_cstride;
+    int32_t dtype;
+    float scale;
+} ymi_attn_desc;
+int ymi_attention(const ymi_attn_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-process (yolort/models/box_head.py:328-360,414-427 + torchvision batched_nms).
  * ymi_postprocess runs, on `stream`, with no host sync:
  *   1. decode   sigmoid, xy=(s*2-0.5+grid)*stride, wh=(s*2)^2*anchor (yolort/models/_utils.py:59-60,
@@ -900,6 +936,9 @@ int ymi_plan_add_post_decode_view(ymi_plan* p, const ymi_post_desc* sink, const 
 /* ymi_dwconv2d as a plan op: the descriptor is checked here (YMI_EINVAL as the direct call), replays under graph capture, is timed by ymi_plan_profile and travels with
  * an exported plan (it is kept in the op record's convolution descriptor: the record's size, which a plan file pins, is unchanged) */
 int ymi_plan_add_dwconv(ymi_plan* p, const ymi_dwconv_desc* d);
+/* ymi_attention as a plan op, on the same terms: checked here, captured, profiled, exported (q / k / v / o ride in the op record's convolution pointers x / w / bias /
+ * y, the scale in its generic integer slot 0 as bits) */
+int ymi_plan_add_attention(ymi_plan* p, const ymi_attn_desc* d);
 int ymi_plan_num_ops(const ymi_plan* p);
 /* ymi_post_set_classes for every post-process descriptor recorded in the plan that carries YMI_POST_CLASS_FILTER (YMI_EINVAL if none does).  The plan remembers the
  * list: ymi_plan_export stores it, and ymi_plan_import writes the masks again before it returns, so an imported plan filters as the exporting one did; the consumer

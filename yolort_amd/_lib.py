@@ -225,6 +225,19 @@ class DwConvDesc(C.Structure):
 
 DWCONV_TILE = {1: (8, 16), 2: (8, 8)}   # YMI_DWCONV_TILE_H x YMI_DWCONV_TILE_W_S<stride>: the output tile of a workgroup
 
+
+class AttnDesc(C.Structure):
+    """ymi_attn_desc: the q / k / v / o views (n, S, heads * d) with their pixel strides, the geometry and the score scale of one self-attention launch (ymi_attention)"""
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p),
+        ("n", C.c_int32), ("S", C.c_int32), ("heads", C.c_int32), ("d", C.c_int32), ("c", C.c_int32),
+        ("q_cstride", C.c_int32), ("k_cstride", C.c_int32), ("v_cstride", C.c_int32), ("o_cstride", C.c_int32), ("dtype", C.c_int32), ("scale", C.c_float),
+    ]
+
+
+ATTN_TILE = (64, 64)          # (YMI_ATTN_TILE_Q, YMI_ATTN_TILE_K): queries per workgroup, keys per LDS chunk
+ATTN_HEAD_DIMS = (32, 64, 128)
+
 CLASSIFY_MAX_MAPS, CLASSIFY_MAX_K, CLASSIFY_LOGITS, CLASSIFY_HIDDEN_LOGITS = 4, 2496, 0, 1   # YMI_CLASSIFY_*
 FILTER_STATUS_BAD_COUNT, FILTER_STATUS_TOTAL, FILTER_STATUS_CAPACITY, FILTER_MAX_K = 1, 2, 4, 32768   # YMI_FILTER_*
 
@@ -310,6 +323,8 @@ _SIGS = {
     "ymi_second_stage_filter": (C.c_int, [C.POINTER(FilterDesc), C.c_void_p]),
     "ymi_dwconv2d": (C.c_int, [C.POINTER(DwConvDesc), C.c_void_p]),
     "ymi_plan_add_dwconv": (C.c_int, [C.c_void_p, C.POINTER(DwConvDesc)]),
+    "ymi_attention": (C.c_int, [C.POINTER(AttnDesc), C.c_void_p]),
+    "ymi_plan_add_attention": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc)]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),

@@ -64,8 +64,10 @@ int conv_head_decode_group_launch(const ymi_conv_desc* descs, int n_levels, cons
 int post_decode_view_launch(const ymi_post_desc* d, const ymi_post_view* v, hipStream_t s);
 int dwconv_check(const ymi_dwconv_desc* d);
 int dwconv_launch(const ymi_dwconv_desc* d, hipStream_t s);
+int attention_check(const ymi_attn_desc* d);
+int attention_launch(const ymi_attn_desc* d, hipStream_t s);
 
-enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW, OP_DWCONV };
+enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW, OP_DWCONV, OP_ATTENTION };
 
 struct Op {
     OpKind kind;
@@ -90,6 +92,18 @@ static ymi_dwconv_desc dwconv_of(const ymi_conv_desc& c) {
     return d;
 }
 
+// OP_ATTENTION likewise: q / k / v / o in conv.x / w / bias / y (relocated with them), S in h, heads in w_in, d in cin, c in cout, the strides of q / k / v / o in
+// x_cstride / res_cstride / y2_cstride / y_cstride, the scale's bits in i[0]
+static ymi_attn_desc attn_of(const Op& op) {
+    const ymi_conv_desc& c = op.conv;
+    ymi_attn_desc d;
+    d.q = c.x; d.k = c.w; d.v = c.bias; d.o = c.y;
+    d.n = c.n; d.S = c.h; d.heads = c.w_in; d.d = c.cin; d.c = c.cout;
+    d.q_cstride = c.x_cstride; d.k_cstride = c.res_cstride; d.v_cstride = c.y2_cstride; d.o_cstride = c.y_cstride; d.dtype = c.dtype;
+    memcpy(&d.scale, &op.i[0], sizeof(float));
+    return d;
+}
+
 static int run_op(const Op& op, hipStream_t s) {
     switch (op.kind) {
         case OP_CONV: return conv2d_launch(&op.conv, s);
@@ -108,6 +122,10 @@ static int run_op(const Op& op, hipStream_t s) {
         case OP_DWCONV: {
             const ymi_dwconv_desc d = dwconv_of(op.conv);
             return dwconv_launch(&d, s);
+        }
+        case OP_ATTENTION: {
+            const ymi_attn_desc d = attn_of(op);
+            return attention_launch(&d, s);
         }
     }
     set_error("unknown op kind");
@@ -354,6 +372,22 @@ extern "C" int ymi_plan_add_dwconv(ymi_plan* p, const ymi_dwconv_desc* d) {
     c.x = d->x; c.w = d->w; c.bias = d->bias; c.y = d->y; c.res = d->res;
     c.n = d->n; c.h = d->h; c.w_in = d->w_in; c.cin = d->c; c.x_cstride = d->x_cstride; c.y_cstride = d->y_cstride; c.res_cstride = d->res_cstride;
     c.ho = d->ho; c.wo = d->wo; c.kh = d->k; c.sh = d->s; c.ph = d->p; c.act = d->act; c.dtype = d->dtype;
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
+extern "C" int ymi_plan_add_attention(ymi_plan* p, const ymi_attn_desc* d) {
+    YMI_REQUIRE(p && d, "ymi_plan_add_attention: null argument");
+    if (const int rc = attention_check(d)) return rc;
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_ATTENTION;
+    ymi_conv_desc& c = op.conv;
+    c.x = d->q; c.w = d->k; c.bias = (const float*)d->v; c.y = d->o;
+    c.n = d->n; c.h = d->S; c.w_in = d->heads; c.cin = d->d; c.cout = d->c;
+    c.x_cstride = d->q_cstride; c.res_cstride = d->k_cstride; c.y2_cstride = d->v_cstride; c.y_cstride = d->o_cstride; c.dtype = d->dtype;
+    memcpy(&op.i[0], &d->scale, sizeof(float));
     p->ops.push_back(op);
     drop_graph(p);
     return (int)p->ops.size() - 1;

@@ -139,6 +139,19 @@ class PackedDWConv:
         self._ktabs: Dict[Tuple[int, int], Tensor] = {}   # (none: Plan.export walks packed weights of both kinds alike)
 
 
+def fold_linear(chains: Sequence[Sequence[Tensor]], bias: Optional[Tensor], dtype: torch.dtype, device: torch.device) -> PackedConv:
+    """nn.Linear maps on an NHWC map as ONE biased 1 x 1 convolution.  A chain holds the weights of maps applied one after the other with nothing between them (the
+    order they are applied in): their matrices are multiplied in float64 and the product is rounded ONCE to `dtype` (PackedConv's fp32 staging of a 16-bit value is
+    exact).  Several chains that read the same input are stacked along the output channels (q, k, v); `bias` covers the stacked outputs."""
+    rows = []
+    for chain in chains:
+        w = chain[0].detach().to(device=device, dtype=torch.float64)
+        for nxt in chain[1:]:
+            w = nxt.detach().to(device=device, dtype=torch.float64) @ w
+        rows.append(w)
+    return PackedConv(torch.cat(rows).to(dtype)[:, :, None, None], bias, None, dtype, device)
+
+
 _TILE_TABLE: Optional[Dict[str, int]] = None
 TILE_TABLE_PATH = os.environ.get("YOLORT_AMD_TILE_TABLE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "tiles_gfx950.json")   # override: A/B runs only
 
@@ -423,6 +436,28 @@ class Plan:
         self._record(self.lib.ymi_plan_add_dwconv(self.handle, C.byref(d)), name, kind="dwconv", flops=2.0 * x.n * ho * wo * pd.c * k * k,
                      bytes=float((x.n * x.h * x.w + x.n * ho * wo * (2 if res is not None else 1)) * pd.c * esz + k * k * pd.c * esz),
                      shape=f"dw{pd.c} k{k}x{k} s{stride} {x.h}x{x.w}->{ho}x{wo}")
+        return out
+
+    def attention(self, q: View, k: View, v: View, heads: int, out: Optional[View] = None, scale: Optional[float] = None, name: str = "attention") -> View:
+        """out[n, i, h] = softmax_j(scale * q[n, i, h] . k[n, j, h]) @ v[n, j, h] over the H * W pixels of the views (ymi_attention, csrc/attention.hip): heads of
+        d = c / heads in {32, 64, 128} channels, scale = d ** -0.5 unless given.  `q`, `k`, `v` and `out` may be channel slices of wider buffers."""
+        if self.fp32:
+            raise YmiError(f"{name}: the fp32 parity mode has no attention kernel (compute in float16 or bfloat16)")
+        if heads < 1 or q.c % heads or q.c // heads not in _lib.ATTN_HEAD_DIMS:
+            raise YmiError(f"{name}: {q.c} channels in {heads} heads: the head dimension must be one of {_lib.ATTN_HEAD_DIMS}")
+        if out is None:
+            out = self.alloc(q.n, q.h, q.w, q.c)
+        if any((t.n, t.h, t.w, t.c) != (q.n, q.h, q.w, q.c) or t.dtype != self.dtype for t in (q, k, v, out)):
+            raise YmiError(f"{name}: q, k, v and the output must be {self.dtype} views of one shape")
+        d = _lib.AttnDesc()
+        d.q, d.k, d.v, d.o = q.ptr, k.ptr, v.ptr, out.ptr
+        d.n, d.S, d.heads, d.d, d.c = q.n, q.h * q.w, heads, q.c // heads, q.c
+        d.q_cstride, d.k_cstride, d.v_cstride, d.o_cstride, d.dtype = q.cs, k.cs, v.cs, out.cs, dtype_code(self.dtype)
+        d.scale = float(d.d) ** -0.5 if scale is None else float(scale)
+        self.keep.append(d)
+        self.io[self.num_ops] = {"name": name, "x": q, "k": k, "v": v, "y": out, "res": None}
+        self._record(self.lib.ymi_plan_add_attention(self.handle, C.byref(d)), name, kind="attention", flops=4.0 * q.n * heads * d.S * d.S * d.d,
+                     bytes=float(4 * q.n * d.S * q.c * out.base.element_size()), shape=f"attn{q.c} h{heads} d{d.d} {q.h}x{q.w}")
         return out
 
     def _pinned_ok(self, d: ConvDesc, tile: int) -> bool:

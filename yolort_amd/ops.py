@@ -746,3 +746,44 @@ def second_stage_filter(boxes: Tensor, scores: Tensor, labels: Tensor, counts: T
     d.n, d.k, d.cap, d.nc2 = n, k, int(lg.shape[0]), int(lg.shape[1])
     check(lib.ymi_second_stage_filter(C.byref(d), _lib.stream_ptr()), "ymi_second_stage_filter")
     return ob, os_, ol, oc, cls2, status
+
+
+def _pixel_stride(t: Tensor) -> Optional[int]:
+    """the pixel stride of an (n, S, c) / (n, H, W, c) tensor that is one NHWC view -- channels contiguous, every outer dimension a whole multiple of the next -- or None"""
+    if t.stride(-1) != 1 and t.shape[-1] > 1:
+        return None
+    lead = [(size, st) for size, st in zip(t.shape[:-1], t.stride()[:-1]) if size > 1]
+    cs = lead[-1][1] if lead else t.shape[-1]
+    span = cs
+    for size, st in reversed(lead):
+        if st != span:
+            return None
+        span *= size
+    return cs if cs >= t.shape[-1] and cs % 8 == 0 and t.data_ptr() % 16 == 0 else None
+
+
+def attention(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: Optional[float] = None) -> Tensor:
+    """Multi-head self-attention on the MI355X: out[n, i, h] = softmax_j(scale * q[n, i, h] . k[n, j, h]) @ v[n, j, h] (ymi_attention, csrc/attention.hip; contract
+    and arithmetic in include/yolort_amd.h).  q, k, v: float16 / bfloat16 device tensors of one shape (n, S, c) or (n, H, W, c), heads of d = c / heads in
+    {32, 64, 128} channels side by side; scale defaults to d ** -0.5.  Strided views are read in place when they are NHWC views (contiguous channels, a pixel
+    stride that is a multiple of 8, a 16-byte aligned start) -- three slices of one qkv tensor are; anything else is copied once.  Returns a contiguous tensor of
+    q's shape.  One launch on the current stream, no synchronisation, no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    if not (q.is_cuda and k.is_cuda and v.is_cuda):
+        raise YmiError("attention runs on an MI355X only (no CPU fallback)")
+    if q.dim() not in (3, 4) or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise YmiError(f"attention: q, k, v must share one shape (n, S, c) or (n, H, W, c) and one dtype, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise YmiError(f"attention computes in float16 or bfloat16, got {q.dtype}")
+    n, c = q.shape[0], q.shape[-1]
+    tokens = q.numel() // max(n * c, 1)
+    if heads < 1 or c % heads or c // heads not in _lib.ATTN_HEAD_DIMS:
+        raise YmiError(f"attention: {c} channels in {heads} heads: the head dimension must be one of {_lib.ATTN_HEAD_DIMS}")
+    ts = [t.detach() if _pixel_stride(t) is not None else t.detach().contiguous() for t in (q, k, v)]
+    out = torch.empty(q.shape, device=q.device, dtype=q.dtype)
+    d = _lib.AttnDesc(q=ts[0].data_ptr(), k=ts[1].data_ptr(), v=ts[2].data_ptr(), o=out.data_ptr(), n=n, S=tokens, heads=heads, d=c // heads, c=c,
+                      q_cstride=_pixel_stride(ts[0]), k_cstride=_pixel_stride(ts[1]), v_cstride=_pixel_stride(ts[2]), o_cstride=c, dtype=_lib.dtype_code(q.dtype),
+                      scale=float(c // heads) ** -0.5 if scale is None else float(scale))
+    with torch.cuda.device(q.device):
+        check(lib.ymi_attention(C.byref(d), _lib.stream_ptr()), "ymi_attention")
+    return out

@@ -2,9 +2,10 @@
 
 Same constructor signatures, attribute names and state_dict keys as the reference's blocks
 (yolort/v5/models/common.py: Conv :42, DWConv :76, Bottleneck :94, BottleneckCSP :119, C3 :149, SPP :176, SPPF :190, Focus :210, C3Ghost :378, GhostConv :386,
-GhostBottleneck :399) so that its
+GhostBottleneck :399, TransformerLayer :308, TransformerBlock :334, C3TR :362) so that its
 checkpoints load unchanged; the arithmetic is the fused implicit-GEMM kernel (csrc/conv_igemm.hip)
-instead of conv2d -> BatchNorm2d -> SiLU -> cat, and the depthwise kernel (csrc/dwconv.hip) for the convolutions with groups == channels.
+instead of conv2d -> BatchNorm2d -> SiLU -> cat, and the depthwise kernel (csrc/dwconv.hip) for the convolutions with groups == channels, and the
+attention kernel (csrc/attention.hip) for nn.MultiheadAttention.
 """
 from __future__ import annotations
 
@@ -17,11 +18,11 @@ import torch
 from torch import nn
 
 from ..._lib import ACT_HARDSWISH, ACT_LEAKY, ACT_NONE, ACT_SILU, YmiError
-from ...engine import PackedConv, PackedDWConv, Plan, View
+from ...engine import PackedConv, PackedDWConv, Plan, View, fold_linear
 from ...hipmodule import HipModule
 
-__all__ = ["Conv", "DWConv", "Bottleneck", "BottleneckCSP", "C3", "C3Ghost", "GhostConv", "GhostBottleneck", "SPP", "SPPF", "Focus", "Classify", "autopad", "focus_transform",
-           "space_to_depth"]
+__all__ = ["Conv", "DWConv", "Bottleneck", "BottleneckCSP", "C3", "C3Ghost", "GhostConv", "GhostBottleneck", "SPP", "SPPF", "Focus", "Classify", "TransformerLayer", "TransformerBlock",
+           "C3TR", "autopad", "focus_transform", "space_to_depth"]
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03  # set after construction by the reference (darknetv6.py:110-112)
 
@@ -227,41 +228,42 @@ class C3(HipModule):
 
     def emit(self, plan: Plan, x: View, out: Optional[View] = None, name: str = "c3") -> View:
         c_ = self.cv1.conv.out_channels
-        nb = len(self.m)
+        blocks = list(self.m) if isinstance(self.m, nn.Sequential) else [self.m]   # (C3TR: `m` is one TransformerBlock)
+        nb = len(blocks)
         # default (YOLORT_AMD_FUSE_C3=0 turns it off, engine.Plan.fuse_c3): the whole block in one launch when it is the instance
         # csrc/c3_fused32.hip holds -- 64 -> 64, one shortcut Bottleneck of 32 hidden channels (yolov5s backbone.body.2)
         if (getattr(plan, "fuse_c3", False) and not plan.use_v1 and nb == 1 and c_ == 32 and x.c == 64 and self.cv3.conv.out_channels == 64
-                and isinstance(self.m[0], Bottleneck) and self.m[0].add and self.m[0].cv1.conv.kernel_size == (1, 1) and self.m[0].cv2.conv.kernel_size == (3, 3)
-                and self.m[0].cv2.conv.groups == 1
-                and all(isinstance(c.act, nn.SiLU) for c in (self.cv1, self.cv2, self.cv3, self.m[0].cv1, self.m[0].cv2))
+                and isinstance(blocks[0], Bottleneck) and blocks[0].add and blocks[0].cv1.conv.kernel_size == (1, 1) and blocks[0].cv2.conv.kernel_size == (3, 3)
+                and blocks[0].cv2.conv.groups == 1
+                and all(isinstance(c.act, nn.SiLU) for c in (self.cv1, self.cv2, self.cv3, blocks[0].cv1, blocks[0].cv2))
                 and (out is None or out.cs % 8 == 0) and x.cs % 8 == 0):
-            b0 = self.m[0]
+            b0 = blocks[0]
             return plan.c3_fused(x, self.packed_pair(plan.dtype, plan.device, x.c), b0.cv1.packed(plan.dtype, plan.device, c_),
                                  b0.cv2.packed(plan.dtype, plan.device, c_), self.cv3.packed(plan.dtype, plan.device, 2 * c_), out=out, name=name + ".fused")
         # round 6 (csrc/c3_tile.hip): hidden widths 64 / 128 on maps whose halo strip of whole rows fits the LDS patch -- the whole block in one launch, or
         # one launch per Bottleneck (HEAD, MID ..., TAIL); intermediates of a launch never reach memory, weights stream in fragment order
         if (nb >= 1 and self.cv3.conv.out_channels == 2 * c_ and getattr(plan, "c3_tile_on", False) and plan.c3_tile_ok(x, c_)
                 and all(isinstance(b, Bottleneck) and b.cv1.conv.kernel_size == (1, 1) and b.cv2.conv.kernel_size == (3, 3) and b.cv2.conv.stride == (1, 1)
-                        and b.cv2.conv.groups == 1 and b.cv1.conv.out_channels == c_ and b.cv2.conv.out_channels == c_ and b.add == self.m[0].add
-                        and isinstance(b.cv1.act, nn.SiLU) and isinstance(b.cv2.act, nn.SiLU) for b in self.m)
+                        and b.cv2.conv.groups == 1 and b.cv1.conv.out_channels == c_ and b.cv2.conv.out_channels == c_ and b.add == blocks[0].add
+                        and isinstance(b.cv1.act, nn.SiLU) and isinstance(b.cv2.act, nn.SiLU) for b in blocks)
                 and all(isinstance(c.act, nn.SiLU) for c in (self.cv1, self.cv2, self.cv3)) and (out is None or out.cs % 8 == 0)):
             pk = lambda cv, cin: cv.packed(plan.dtype, plan.device, cin)  # noqa: E731
             pc12, pc3 = self.packed_pair(plan.dtype, plan.device, x.c), pk(self.cv3, 2 * c_)
-            add = bool(self.m[0].add)
+            add = bool(blocks[0].add)
             if nb == 1:
-                return plan.c3_tile(0, pk(self.m[0].cv1, c_), pk(self.m[0].cv2, c_), add, x=x, pc12=pc12, pc3=pc3, out=out, name=name + ".tile")
+                return plan.c3_tile(0, pk(blocks[0].cv1, c_), pk(blocks[0].cv2, c_), add, x=x, pc12=pc12, pc3=pc3, out=out, name=name + ".tile")
             y2 = plan.alloc(x.n, x.h, x.w, c_)
             ping = [plan.alloc(x.n, x.h, x.w, c_), plan.alloc(x.n, x.h, x.w, c_) if nb > 2 else None]
-            cur = plan.c3_tile(1, pk(self.m[0].cv1, c_), pk(self.m[0].cv2, c_), add, x=x, pc12=pc12, y1_out=ping[0], y2=y2, name=name + ".tile.cv1+cv2+m.0")
+            cur = plan.c3_tile(1, pk(blocks[0].cv1, c_), pk(blocks[0].cv2, c_), add, x=x, pc12=pc12, y1_out=ping[0], y2=y2, name=name + ".tile.cv1+cv2+m.0")
             for j in range(1, nb - 1):
-                cur = plan.c3_tile(2, pk(self.m[j].cv1, c_), pk(self.m[j].cv2, c_), add, y1_in=cur, y1_out=ping[j % 2], name=f"{name}.tile.m.{j}")
-            return plan.c3_tile(3, pk(self.m[nb - 1].cv1, c_), pk(self.m[nb - 1].cv2, c_), add, y1_in=cur, y2=y2, pc3=pc3, out=out, name=f"{name}.tile.m.{nb - 1}+cv3")
+                cur = plan.c3_tile(2, pk(blocks[j].cv1, c_), pk(blocks[j].cv2, c_), add, y1_in=cur, y1_out=ping[j % 2], name=f"{name}.tile.m.{j}")
+            return plan.c3_tile(3, pk(blocks[nb - 1].cv1, c_), pk(blocks[nb - 1].cv2, c_), add, y1_in=cur, y2=y2, pc3=pc3, out=out, name=f"{name}.tile.m.{nb - 1}+cv3")
         cat = plan.alloc(x.n, x.h, x.w, 2 * c_)
         fuse = (not plan.use_v1) and c_ % 8 == 0 and nb >= 1 and isinstance(self.cv1.act, nn.SiLU) and isinstance(self.cv2.act, nn.SiLU)
         t0 = None
         if fuse:
             y = plan.alloc(x.n, x.h, x.w, c_)
-            b0 = self.m[0]
+            b0 = blocks[0]
             # the first Bottleneck's 1x1 (cv1) rides in the same launch: its input is this conv's freshly rounded output
             chain_ok = (plan.chain_1x1 and c_ in (32, 64) and   # (K = 128 works in the kernels but costs the main conv more than the saved launch: measured in round 4, not emitted)
                          isinstance(b0, Bottleneck) and isinstance(b0.cv1.act, nn.SiLU) and b0.cv1.conv.kernel_size == (1, 1)
@@ -279,11 +281,11 @@ class C3(HipModule):
         c2 = self.cv3.conv.out_channels
         chain3 = None
         if (fuse and plan.chain_1x1 and plan.chain_cv3 and nb >= 1 and c_ in (32, 64) and c2 % 32 == 0 and c2 <= 128 and isinstance(self.cv3.act, nn.SiLU)
-                and isinstance(self.m[nb - 1], Bottleneck) and self.m[nb - 1].cv2.conv.kernel_size == (3, 3) and self.m[nb - 1].cv2.conv.out_channels == c_):
+                and isinstance(blocks[nb - 1], Bottleneck) and blocks[nb - 1].cv2.conv.kernel_size == (3, 3) and blocks[nb - 1].cv2.conv.out_channels == c_):
             o3 = out if out is not None else plan.alloc(x.n, x.h, x.w, c2)
             chain3 = (self.cv3.packed(plan.dtype, plan.device, 2 * c_), o3, cat.slice_c(c_, c_))
         t_next = None
-        for j, b in enumerate(self.m):
+        for j, b in enumerate(blocks):
             kw = {}
             if j == 0 and t0 is not None:
                 kw["t"] = t0
@@ -292,16 +294,16 @@ class C3(HipModule):
             t_next = None
             if j == nb - 1 and chain3 is not None:
                 kw["chain"] = chain3
-            elif (j < nb - 1 and getattr(plan, "chain_next", False) and (plan.chain_next is True or plan.chain_next == c_) and not plan.use_v1 and c_ in (32, 64, 128) and isinstance(b, Bottleneck) and isinstance(self.m[j + 1], Bottleneck)
+            elif (j < nb - 1 and getattr(plan, "chain_next", False) and (plan.chain_next is True or plan.chain_next == c_) and not plan.use_v1 and c_ in (32, 64, 128) and isinstance(b, Bottleneck) and isinstance(blocks[j + 1], Bottleneck)
                   and b.cv2.conv.kernel_size == (3, 3) and b.cv2.conv.stride == (1, 1) and b.cv2.conv.groups == 1 and b.cv2.conv.out_channels == c_
-                  and isinstance(b.cv2.act, nn.SiLU) and isinstance(self.m[j + 1].cv1.act, nn.SiLU) and self.m[j + 1].cv1.conv.kernel_size == (1, 1)
-                  and self.m[j + 1].cv1.conv.out_channels % 32 == 0 and self.m[j + 1].cv1.conv.out_channels <= 128):
+                  and isinstance(b.cv2.act, nn.SiLU) and isinstance(blocks[j + 1].cv1.act, nn.SiLU) and blocks[j + 1].cv1.conv.kernel_size == (1, 1)
+                  and blocks[j + 1].cv1.conv.out_channels % 32 == 0 and blocks[j + 1].cv1.conv.out_channels <= 128):
                 # this Bottleneck's 3x3 carries the next one's 1x1 in its epilogue (reference :115-116 twice: x + cv2(cv1(x)), then cv1 of the next)
-                nxt = self.m[j + 1]
+                nxt = blocks[j + 1]
                 t_next = plan.alloc(x.n, x.h, x.w, nxt.cv1.conv.out_channels)
                 kw["chain"] = (nxt.cv1.packed(plan.dtype, plan.device, c_), t_next)
                 kw["chain_name"] = f"m.{j + 1}.cv1"
-            y = b.emit(plan, y, out=cat.slice_c(0, c_) if j == nb - 1 else None, name=f"{name}.m.{j}", **kw)
+            y = b.emit(plan, y, out=cat.slice_c(0, c_) if j == nb - 1 else None, name=f"{name}.m.{j}" if isinstance(self.m, nn.Sequential) else name + ".m", **kw)
         if not fuse:
             self.cv2.emit(plan, x, out=cat.slice_c(c_, c_), name=name + ".cv2")
         if chain3 is not None:
@@ -317,6 +319,99 @@ class C3Ghost(C3):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = nn.Sequential(*[GhostBottleneck(c_, c_) for _ in range(n)])
+
+
+def _tensors_sig(*tensors) -> Tuple:
+    return tuple((t._version, t.data_ptr()) for t in tensors)
+
+
+class TransformerLayer(HipModule):
+    """x = ma(q(x), k(x), v(x)) + x;  x = fc2(fc1(x)) + x over the pixels of a map as tokens (reference common.py:308-331; no LayerNorm).  `ma` is an
+    nn.MultiheadAttention kept as the parameter holder (`ma.in_proj_weight`, `ma.in_proj_bias`, `ma.out_proj.*`): its arithmetic is four launches --
+      1. qkv: ONE biased 1 x 1 convolution c -> 3c whose weight is in_proj_weight[part] @ {q, k, v}.weight and whose bias is in_proj_bias.  Two Linear maps with nothing
+         between them are one Linear: the product is taken in float64 at pack time and rounded ONCE, where the reference rounds q(x) to 16 bits between the two;
+      2. the attention kernel (csrc/attention.hip) on the three channel slices of that buffer, the d ** -0.5 as the kernel's `scale`;
+      3. out_proj with its bias and the shortcut x in the epilogue;
+      4. fc2 @ fc1 folded the same way (the reference rounds fc1's output in between), the shortcut in the epilogue.
+    The fold changes which 16-bit roundings happen, not the function: the float64 evaluation of the unfolded module is the yardstick of the tests."""
+
+    def __init__(self, c, num_heads):
+        super().__init__()
+        if c % num_heads or c // num_heads not in (32, 64, 128):
+            raise NotImplementedError(f"the attention kernel implements head dimensions 32, 64 and 128 (got c = {c}, num_heads = {num_heads})")
+        self.q = nn.Linear(c, c, bias=False)
+        self.k = nn.Linear(c, c, bias=False)
+        self.v = nn.Linear(c, c, bias=False)
+        self.ma = nn.MultiheadAttention(embed_dim=c, num_heads=num_heads)
+        self.fc1 = nn.Linear(c, c, bias=False)
+        self.fc2 = nn.Linear(c, c, bias=False)
+        self._packed: Dict[Tuple, Tuple] = {}
+
+    def packed(self, dtype: torch.dtype, device: torch.device) -> Tuple[PackedConv, PackedConv, PackedConv]:
+        """(qkv, out_proj, fc2 @ fc1) as biased 1 x 1 convolutions"""
+        ma = self.ma
+        sig = _tensors_sig(self.q.weight, self.k.weight, self.v.weight, ma.in_proj_weight, ma.in_proj_bias, ma.out_proj.weight, ma.out_proj.bias, self.fc1.weight, self.fc2.weight)
+        hit = self._packed.get((dtype, device))
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        wq, wk, wv = ma.in_proj_weight.chunk(3)
+        pcs = (fold_linear([(self.q.weight, wq), (self.k.weight, wk), (self.v.weight, wv)], ma.in_proj_bias, dtype, device),
+               fold_linear([(ma.out_proj.weight,)], ma.out_proj.bias, dtype, device), fold_linear([(self.fc1.weight, self.fc2.weight)], None, dtype, device))
+        self._packed[(dtype, device)] = (sig, pcs)
+        return pcs
+
+    def emit(self, plan: Plan, x: View, out: Optional[View] = None, name: str = "transformerlayer") -> View:
+        c = self.q.in_features
+        if x.c != c:
+            raise YmiError(f"{name}: input view has {x.c} channels, the layer expects {c}")
+        pc_qkv, pc_out, pc_fc = self.packed(plan.dtype, plan.device)
+        qkv = plan.conv(x, pc_qkv, 1, 0, ACT_NONE, name=name + ".qkv")
+        a = plan.attention(qkv.slice_c(0, c), qkv.slice_c(c, c), qkv.slice_c(2 * c, c), self.ma.num_heads, name=name + ".ma")
+        y = plan.conv(a, pc_out, 1, 0, ACT_NONE, res=x, name=name + ".ma.out_proj")
+        return plan.conv(y, pc_fc, 1, 0, ACT_NONE, out=out, res=y, name=name + ".fc1+fc2")
+
+
+class TransformerBlock(HipModule):
+    """tr(p + linear(p)) on the c2-channel map, after a Conv(c1, c2) when c1 != c2 (reference common.py:334-359).  The reference's flatten / transpose to (S, b, c)
+    tokens is the NHWC view itself: `linear` (the learnable position embedding) is a biased 1 x 1 convolution with the shortcut in its epilogue, then the layers."""
+
+    def __init__(self, c1, c2, num_heads, num_layers):
+        super().__init__()
+        self.conv = None
+        if c1 != c2:
+            self.conv = Conv(c1, c2)
+        self.linear = nn.Linear(c2, c2)
+        self.tr = nn.Sequential(*[TransformerLayer(c2, num_heads) for _ in range(num_layers)])
+        self.c2 = c2
+        self._packed: Dict[Tuple, Tuple] = {}
+
+    @property
+    def out_channels(self) -> int:
+        return self.c2
+
+    def emit(self, plan: Plan, x: View, out: Optional[View] = None, name: str = "transformerblock") -> View:
+        if self.conv is not None:
+            x = self.conv.emit(plan, x, name=name + ".conv")
+        sig = _tensors_sig(self.linear.weight, self.linear.bias)
+        hit = self._packed.get((plan.dtype, plan.device))
+        if hit is None or hit[0] != sig:
+            hit = self._packed[(plan.dtype, plan.device)] = (sig, fold_linear([(self.linear.weight,)], self.linear.bias, plan.dtype, plan.device))
+        nl = len(self.tr)
+        y = plan.conv(x, hit[1], 1, 0, ACT_NONE, out=out if nl == 0 else None, res=x, name=name + ".linear")
+        for i, layer in enumerate(self.tr):
+            y = layer.emit(plan, y, out=out if i == nl - 1 else None, name=f"{name}.tr.{i}")
+        return y
+
+
+class C3TR(C3):
+    """C3 whose `m` is ONE TransformerBlock(c_, c_, 4, n) (reference common.py:362-367).  C3.emit's fused, strip and chained forms test isinstance(..., Bottleneck), so
+    it takes the general path as C3Ghost does: cv1 + cv2 in one launch, the block through its own emit with its last launch writing into the concat half, cv3.
+    Four heads of c_ / 4 channels: c2 * e must be 128, 256 or 512."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = TransformerBlock(c_, c_, 4, n)
 
 
 class BottleneckCSP(HipModule):
