@@ -908,6 +908,66 @@ typedef struct ymi_eval_desc {
 int ymi_eval_match(const ymi_eval_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * YOLOv5 validation matching on the device: the ONE-TO-ONE detection <-> ground-truth assignment by IoU behind the numbers ultralytics' val.py prints -- the
+ * confusion matrix (ConfusionMatrix.process_batch, yolort/v5/utils/metrics.py:133-171) and the per-threshold true-positive flags that ap_per_class (:21-85)
+ * consumes -- for the detection slab, one launch per batch.  It is NOT the COCO matching above: nothing is walked in score order; both use cases form every
+ * admissible pair, keep per detection its best ground truth and then per ground truth its best detection (the two np.unique calls of metrics.py:152-155).
+ * Inputs (device, read-only): the slab and the padded ground truth exactly as ymi_eval_desc takes them (boxes (n, k, 4) fp32 xyxy, scores (n, k) fp32, labels (n, k)
+ * int64, counts (n) int32; gt_boxes (n, g, 4), gt_labels (n, g) int32, gt_counts (n) int32, negative = 0, above g = g).  Slots at or past a count are never read.
+ * Per image:
+ *   - CANDIDATES: detection d takes part iff score(d) > conf (strict; conf = -inf admits every number; a NaN score never passes).
+ *   - IoU = inter / ((area_d + area_g) - inter), inter = max(x2 - x1, 0) * max(y2 - y1, 0) of the intersection: the suppression's own expression (step 3 of the
+ *     post-process above, torchvision's box_iou), every operation a rounded fp32 one, the division correctly rounded, no epsilon.  Two zero-area boxes give 0 / 0 = NaN,
+ *     and NaN never passes a test here; a zero quotient is +0.
+ *   - ADMISSIBLE PAIRS, thr0 = thrs[0]: class_aware == 0 ("matrix" mode, metrics.py:148): IoU > thr0, strict, ANY classes;
+ *     class_aware != 0 ("tp" mode, val.py's process_batch): IoU >= thr0 and label(d) == class(g).
+ *   - PASS 1: every candidate keeps its admissible ground truth of the largest IoU; ties go to the LOWEST ground-truth index.
+ *   - PASS 2: every ground truth keeps, among the detections that chose it in pass 1, the one of the largest IoU; ties go to the LOWEST slab slot.
+ *   - A detection displaced in pass 2 stays UNMATCHED: it does not fall back to its second-best ground truth (what the two np.unique calls do).
+ *   - The tie rule is this library's: the reference sorts with an unstable argsort and leaves ties open.
+ * Outputs (device), written for EVERY slot of the slab (a slot at or past its count, a non-candidate, a skipped detection and every slot of a skipped image hold
+ * -1 / 0 / 0): match (n, k) int32 = the matched ground-truth index or -1; iou (n, k) fp32 = the matched IoU (0 when unmatched); tp (n, k, num_thrs) uint8 with
+ * tp[d][t] = matched && IoU >= thrs[t] (fp32 compare, as torch's `iou >= iouv[t]`); 1 <= num_thrs <= YMI_VAL_MAX_THRS, each threshold in [0, 1].
+ * matrix (optional, NULL = none): int32 (nc + 1, nc + 1) in device memory, matrix[pred][true], ADDED to (the caller zeroes it once and accumulates over launches):
+ *   - a matched ground truth of class c adds 1 to [label(d)][c], d its detection; an unmatched ground truth adds 1 to [nc][c];
+ *   - an unmatched CANDIDATE detection adds 1 to [label(d)][nc], but only if its image has at least one match -- the quirk of metrics.py:168-171, kept;
+ *     YMI_VAL_COUNT_ALL_FP in `flags` switches it off (every unmatched candidate counts);
+ *   - the additions are integer vector atomics: the result does not depend on any order.
+ * status: int32[4]; the kernel only ever ORs bits into status[1] (the caller zeroes it): YMI_VAL_STATUS_BAD_LABEL -- a label below a count outside [0, num_classes):
+ * that detection or ground truth is skipped (takes no part, counts nowhere) --, YMI_VAL_STATUS_BAD_COUNT -- a counts[i] above k, taken as k --,
+ * YMI_VAL_STATUS_STALE_ROW -- a negative counts[i] (YMI_SLAB_STALE): the image is skipped altogether, its ground truth included.
+ * k, g <= YMI_VAL_MAX_PER_IMAGE, num_classes <= 4096; anything larger is refused with YMI_EINVAL, not truncated.  One workgroup per image (val_match_kernel,
+ * csrc/val_match.hip); no workspace; the launch is ordered on `stream`, synchronises nothing, reads nothing back and may be captured.  ABI stays 6: a new struct
+ * and a new function. */
+#define YMI_VAL_MAX_THRS 10
+#define YMI_VAL_MAX_PER_IMAGE 1024
+#define YMI_VAL_STATUS_BAD_LABEL 1 /* status[1] bit 0 */
+#define YMI_VAL_STATUS_STALE_ROW 2 /* status[1] bit 1 */
+#define YMI_VAL_STATUS_BAD_COUNT 4 /* status[1] bit 2 */
+#define YMI_VAL_COUNT_ALL_FP 1     /* flags bit 0 */
+typedef struct ymi_val_desc {
+    const float* boxes;
+    const float* scores;
+    const int64_t* labels;
+    const int32_t* counts;
+    const float* gt_boxes;
+    const int32_t* gt_labels;
+    const int32_t* gt_counts;
+    int32_t* match;
+    float* iou;
+    uint8_t* tp;
+    int32_t* matrix;
+    int32_t* status;
+    float thrs[YMI_VAL_MAX_THRS];
+    float conf;
+    int32_t n, k, g;
+    int32_t num_thrs, num_classes;
+    int32_t class_aware, flags;
+    int32_t reserved[2];
+} ymi_val_desc;
+int ymi_val_match(const ymi_val_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Plan: a recorded sequence of the launches above for one (arch, N, H, W, dtype), replayed with a
  * single call (and optionally captured into a hipGraph).  Replaces the Python module-by-module
  * dispatch of yolort/models/yolo.py:159-175.  The plan copies descriptors; buffers stay owned by

@@ -122,6 +122,23 @@ class EvalDesc(C.Structure):
     ]
 
 
+VAL_MAX_THRS, VAL_MAX_PER_IMAGE = 10, 1024                                        # YMI_VAL_MAX_*
+VAL_STATUS_BAD_LABEL, VAL_STATUS_STALE_ROW, VAL_STATUS_BAD_COUNT = 1, 2, 4        # YMI_VAL_STATUS_*: bits of status[1]
+VAL_COUNT_ALL_FP = 1                                                              # YMI_VAL_COUNT_ALL_FP: bit of flags
+
+
+class ValDesc(C.Structure):
+    """ymi_val_desc: the detection slab, the padded ground truth, the outputs, the optional confusion matrix and the rule (conf, thresholds, mode) of one ymi_val_match launch"""
+    _fields_ = [
+        ("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p),
+        ("gt_boxes", C.c_void_p), ("gt_labels", C.c_void_p), ("gt_counts", C.c_void_p),
+        ("match", C.c_void_p), ("iou", C.c_void_p), ("tp", C.c_void_p), ("matrix", C.c_void_p), ("status", C.c_void_p),
+        ("thrs", C.c_float * VAL_MAX_THRS), ("conf", C.c_float),
+        ("n", C.c_int32), ("k", C.c_int32), ("g", C.c_int32), ("num_thrs", C.c_int32), ("num_classes", C.c_int32),
+        ("class_aware", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
 CROP_STATUS_CAPACITY, CROP_STATUS_BAD_COUNT = 1, 2   # YMI_CROP_STATUS_*: bits of total[1]
 
 
@@ -315,6 +332,7 @@ _SIGS = {
     "ymi_batched_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ymi_eval_match": (C.c_int, [C.POINTER(EvalDesc), C.c_void_p]),
+    "ymi_val_match": (C.c_int, [C.POINTER(ValDesc), C.c_void_p]),
     "ymi_crop_resize": (C.c_int, [C.POINTER(CropDesc), C.c_void_p]),
     "ymi_render": (C.c_int, [C.POINTER(RenderDesc), C.c_void_p]),
     "ymi_render_nv12": (C.c_int, [C.POINTER(RenderNv12Desc), C.c_void_p]),

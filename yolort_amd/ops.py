@@ -127,6 +127,60 @@ def match_detections(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tens
     return tp, ig, rank, n_gt
 
 
+def val_match(boxes: Tensor, scores: Tensor, labels: Tensor, counts: Tensor, gt_boxes: Tensor, gt_labels: Tensor, gt_counts: Tensor, num_classes: int, *,
+              conf: float, thrs: Sequence[float], class_aware: bool, matrix: Optional[Tensor] = None, status: Optional[Tensor] = None, count_all_fp: bool = False):
+    """The one-to-one matching by IoU of YOLOv5's val.py on the MI355X (ymi_val_match, include/yolort_amd.h): the detection slab (boxes (N,K,4), scores (N,K), labels
+    (N,K) int64, counts (N)) against padded ground truth (gt_boxes (N,G,4), gt_labels (N,G), gt_counts (N)) -> (match (N,K) int32: the matched ground-truth index or
+    -1, iou (N,K) fp32: the matched IoU, tp (N,K,T) uint8: matched and IoU >= thrs[t], status int32[4]) on the device.  A detection takes part iff score > conf
+    (-inf: all); thrs are at most 10 fp32 thresholds in [0, 1], thrs[0] the admission threshold: class_aware=False admits IoU > thrs[0] between ANY classes (the
+    confusion matrix's rule), class_aware=True IoU >= thrs[0] within a class (the rule behind ap_per_class).  Each detection keeps its best admissible ground truth
+    (ties: lowest index), each ground truth its best such detection (ties: lowest slot); a displaced detection stays unmatched.  `matrix`: an int32 (C+1, C+1) device
+    tensor ADDED to, matrix[pred, true], background last; an unmatched candidate counts as [label, C] only in an image with at least one match (the reference's
+    quirk) unless count_all_fp.  `status` (int32[4], zeroed by the caller) is ORed into: status[1] holds _lib.VAL_STATUS_* bits.  K, G <= 1024, C <= 4096.  One launch
+    on the current stream, no synchronisation, nothing read back (capturable).  No CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    if not all(t.is_cuda for t in (boxes, scores, labels, counts, gt_boxes, gt_labels, gt_counts)):
+        raise YmiError("val_match runs on an MI355X only (no CPU fallback)")
+    n, k = int(scores.shape[0]), int(scores.shape[1])
+    g = int(gt_labels.shape[1])
+    if tuple(boxes.shape) != (n, k, 4) or tuple(labels.shape) != (n, k) or tuple(counts.shape) != (n,):
+        raise YmiError(f"val_match: expected the slab (N,K,4) / (N,K) / (N,K) / (N), got {tuple(boxes.shape)} {tuple(scores.shape)} {tuple(labels.shape)} {tuple(counts.shape)}")
+    if tuple(gt_boxes.shape) != (n, g, 4) or tuple(gt_counts.shape) != (n,):
+        raise YmiError(f"val_match: expected ground truth (N,G,4) / (N,G) / (N), got {tuple(gt_boxes.shape)} {tuple(gt_labels.shape)} {tuple(gt_counts.shape)}")
+    thrs = [float(t) for t in thrs]
+    nc, dev = int(num_classes), boxes.device
+    d = _lib.ValDesc()
+    d.n, d.k, d.g, d.num_thrs, d.num_classes = n, k, g, len(thrs), nc
+    d.class_aware, d.flags, d.conf = int(bool(class_aware)), (_lib.VAL_COUNT_ALL_FP if count_all_fp else 0), float(conf)
+    for i, t in enumerate(thrs[:_lib.VAL_MAX_THRS]):
+        d.thrs[i] = t
+    nt = max(min(len(thrs), _lib.VAL_MAX_THRS), 1)
+    match = torch.empty(n, k, device=dev, dtype=torch.int32)
+    iou = torch.empty(n, k, device=dev, dtype=torch.float32)
+    tp = torch.empty(n, k, nt, device=dev, dtype=torch.uint8)
+    status = torch.zeros(4, device=dev, dtype=torch.int32) if status is None else status
+    for t, shape, name in ((matrix, (nc + 1, nc + 1), "matrix"), (status, (4,), "status")):
+        if t is not None and (not t.is_cuda or tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_contiguous()):
+            raise YmiError(f"val_match: {name} must be a contiguous int32 device tensor of shape {shape}")
+    ins = [boxes.detach().to(torch.float32).contiguous(), scores.detach().to(torch.float32).contiguous(), labels.detach().to(torch.int64).contiguous(),
+           counts.detach().to(torch.int32).contiguous(), gt_boxes.detach().to(torch.float32).contiguous(), gt_labels.detach().to(torch.int32).contiguous(),
+           gt_counts.detach().to(torch.int32).contiguous()]
+    d.boxes, d.scores, d.labels, d.counts, d.gt_boxes, d.gt_labels, d.gt_counts = [t.data_ptr() for t in ins]
+    d.match, d.iou, d.tp, d.status = match.data_ptr(), iou.data_ptr(), tp.data_ptr(), status.data_ptr()
+    d.matrix = matrix.data_ptr() if matrix is not None else None
+    check(lib.ymi_val_match(C.byref(d), _lib.stream_ptr()), "ymi_val_match")
+    return match, iou, tp, status
+
+
+def _raise_val_status(bits: int) -> None:
+    if bits & _lib.VAL_STATUS_STALE_ROW:
+        raise ValueError("the slab still holds a stale shard: take PendingDetections.gathered() (it resolves the second round) first")
+    if bits & _lib.VAL_STATUS_BAD_LABEL:
+        raise ValueError("a detection or ground-truth label lies outside [0, num_classes)")
+    if bits & _lib.VAL_STATUS_BAD_COUNT:
+        raise ValueError("a slab count exceeds the slab's K slots")
+
+
 def nv12_planes(frame):
     """A video frame in NV12 -> (y, uv, h, w): the Y plane (h, w) and the CbCr plane (h / 2, w) as 2-D uint8 views with stride(1) == 1 (the row stride is the pitch).
     `frame` is the packed buffer -- a contiguous 2-D uint8 tensor (3h / 2, w): Y rows, then chroma rows -- or a pair (y, uv) of such views, which is how pitched decoder

@@ -8,6 +8,10 @@ applies it -- its exact threshold grid linspace(.5, .95, 10) and its small / med
 COCOeval.evaluateImg) are applied; crowd boxes are not modelled (the in-memory ground truth has none).  `update_from_slab`
 feeds the evaluator from the fixed-shape detection slab the ranks all-gather (yolort_amd/dist.py), so every rank scores the
 GLOBAL batch without the reference's pickle exchange (yolort/data/coco_eval.py:225-226 -> data/distributed.py:6-49).
+
+The second protocol is YOLOv5's own (yolort/v5/utils/metrics.py:21-171, what ultralytics' val.py prints): `ap_per_class` / `compute_ap` / `val_summary` restate
+its precision / recall / F1 / mAP accumulation in float64 on the host; `ValEvaluator` and `ConfusionMatrix` run its one-to-one matching by IoU -- a different rule
+from COCO's greedy walk -- on the device (ops.val_match) and hand the flags to that accumulation.
 """
 from __future__ import annotations
 
@@ -336,3 +340,196 @@ class GpuDetectionEvaluator:
 
         return {"AP": f(ap(0, self._ap_idx)), "AP50": f(ap(0, [self._i50])), "AP75": f(ap(0, [self._i75])),
                 "APs": f(ap(1, self._ap_idx)), "APm": f(ap(2, self._ap_idx)), "APl": f(ap(3, self._ap_idx))}
+
+
+# ---- YOLOv5's validation numbers: precision / recall / F1 / mAP@0.5 / mAP@0.5:0.95 per class and the confusion matrix (yolort/v5/utils/metrics.py:21-171) ----------
+VAL_IOUV = np.linspace(0.5, 0.95, 10)   # val.py's iouv (torch.linspace(0.5, 0.95, 10)); the device compares against these values rounded to fp32
+
+
+def compute_ap(recall, precision):
+    """metrics.py:88-121 (method 'interp'): sentinels, the precision envelope, then the trapezoid rule over the 101-point interpolation -> (ap, mpre, mrec), float64"""
+    mrec = np.concatenate(([0.0], np.asarray(recall, np.float64), [1.0]))
+    mpre = np.concatenate(([1.0], np.asarray(precision, np.float64), [0.0]))
+    mpre = np.flip(np.maximum.accumulate(np.flip(mpre)))
+    x = np.linspace(0, 1, 101)
+    y = np.interp(x, mrec, mpre)
+    ap = float(np.sum((y[1:] + y[:-1]) * 0.5 * np.diff(x)))   # np.trapz(y, x)
+    return ap, mpre, mrec
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls):
+    """metrics.py:21-85 without the plots, in float64 on the host: tp (n, T) true-positive flags per IoU threshold, conf (n) scores, pred_cls (n) predicted classes,
+    target_cls (m) ground-truth classes -> (p, r, ap, f1, unique_classes): precision, recall and F1 per ground-truth class at the confidence of the best mean F1,
+    ap (classes, T).  The score sort is stable (the reference's argsort leaves equal scores open); a class without predictions keeps zeros."""
+    tp = np.asarray(tp, np.float64).reshape(len(conf), -1)
+    conf, pred_cls, target_cls = np.asarray(conf, np.float64), np.asarray(pred_cls), np.asarray(target_cls)
+    i = np.argsort(-conf, kind="stable")
+    tp, conf, pred_cls = tp[i], conf[i], pred_cls[i]
+    unique_classes = np.unique(target_cls)
+    nc = unique_classes.shape[0]
+    px = np.linspace(0, 1, 1000)
+    ap, p, r = np.zeros((nc, tp.shape[1])), np.zeros((nc, 1000)), np.zeros((nc, 1000))
+    for ci, c in enumerate(unique_classes):
+        i = pred_cls == c
+        n_l = int((target_cls == c).sum())
+        n_p = int(i.sum())
+        if n_p == 0 or n_l == 0:
+            continue
+        fpc = (1 - tp[i]).cumsum(0)
+        tpc = tp[i].cumsum(0)
+        recall = tpc / (n_l + 1e-16)
+        r[ci] = np.interp(-px, -conf[i], recall[:, 0], left=0)   # negative x: xp must increase
+        precision = tpc / (tpc + fpc)
+        p[ci] = np.interp(-px, -conf[i], precision[:, 0], left=1)
+        for j in range(tp.shape[1]):
+            ap[ci, j] = compute_ap(recall[:, j], precision[:, j])[0]
+    f1 = 2 * p * r / (p + r + 1e-16)
+    i = int(f1.mean(0).argmax()) if nc else 0
+    return p[:, i], r[:, i], ap, f1[:, i], unique_classes.astype("int32")
+
+
+def val_summary(tp, conf, pred_cls, target_cls) -> Dict:
+    """val.py's summary of the accumulated statistics: mean precision / recall / F1 at the best-F1 confidence, map50, map (mean AP over the thresholds) over the classes
+    that have ground truth, those classes (ap_class) and the per-class lists behind the means.  Zeros and empty lists when nothing can be scored (no true positive at
+    the first threshold: val.py's `stats[0].any()`)."""
+    tp = np.asarray(tp)
+    if not len(tp) or not tp.any():
+        return {"precision": 0.0, "recall": 0.0, "f1": 0.0, "map50": 0.0, "map": 0.0, "ap_class": [], "p_class": [], "r_class": [], "f1_class": [], "ap50_class": [],
+                "map_class": []}
+    p, r, ap, f1, cls = ap_per_class(tp, conf, pred_cls, target_cls)
+    ap50, apm = ap[:, 0], ap.mean(1)
+    return {"precision": float(p.mean()), "recall": float(r.mean()), "f1": float(f1.mean()), "map50": float(ap50.mean()), "map": float(apm.mean()),
+            "ap_class": [int(c) for c in cls], "p_class": [float(v) for v in p], "r_class": [float(v) for v in r], "f1_class": [float(v) for v in f1],
+            "ap50_class": [float(v) for v in ap50], "map_class": [float(v) for v in apm]}
+
+
+def _pad_preds(preds):
+    """List[Dict{boxes (k,4), scores (k), labels (k)}] of device tensors -> the slab (boxes (N,K,4), scores (N,K), labels (N,K) int64, counts (N) int32)"""
+    import torch
+    dev = preds[0]["boxes"].device
+    lens = [int(p["scores"].shape[0]) for p in preds]
+    k = max(lens + [1])
+    boxes = torch.zeros(len(preds), k, 4, device=dev, dtype=torch.float32)
+    scores = torch.zeros(len(preds), k, device=dev, dtype=torch.float32)
+    labels = torch.zeros(len(preds), k, device=dev, dtype=torch.int64)
+    for i, p in enumerate(preds):
+        if lens[i]:
+            boxes[i, : lens[i]] = p["boxes"].detach().to(torch.float32)
+            scores[i, : lens[i]] = p["scores"].detach().to(torch.float32)
+            labels[i, : lens[i]] = p["labels"].detach().to(torch.int64)
+    return boxes, scores, labels, torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
+
+
+class ConfusionMatrix:
+    """The reference's ConfusionMatrix (metrics.py:124-171) with the matching and the counting on the MI355X (ops.val_match, class_aware=False): detections above `conf`
+    against ground truth, pairs of IoU > iou_thres between any classes, one-to-one by IoU; matrix[pred, true] with the background as row / column nc.  An unmatched
+    detection counts as [label, nc] only in an image with at least one match, as the reference has it (count_all_fp=True: always).  Every call enqueues one launch
+    and reads nothing back; `.matrix` makes the one transfer.  At most 1024 detections and 1024 ground truths per image; no CPU fallback."""
+
+    def __init__(self, nc: int, conf: float = 0.25, iou_thres: float = 0.45, count_all_fp: bool = False):
+        self.nc, self.conf, self.iou_thres, self.count_all_fp = int(nc), conf, iou_thres, count_all_fp
+        self._matrix = None   # (nc + 1, nc + 1) int32 on the device, added to by every launch
+        self._status = None
+
+    def update_from_slab(self, slab, targets) -> None:
+        """slab = (boxes (N,K,4), scores (N,K), labels (N,K), counts (N)) on the device; targets as GpuDetectionEvaluator.update_from_slab takes them"""
+        import torch
+        from .. import ops
+        boxes, scores, labels, counts = slab
+        if int(scores.shape[0]) == 0:
+            return
+        gb, gl, gc = GpuDetectionEvaluator._pad_targets(targets, boxes.device)
+        if self._matrix is None:
+            self._matrix = torch.zeros(self.nc + 1, self.nc + 1, device=boxes.device, dtype=torch.int32)
+            self._status = torch.zeros(4, device=boxes.device, dtype=torch.int32)
+        ops.val_match(boxes, scores, labels, counts, gb, gl, gc, self.nc, conf=self.conf, thrs=[self.iou_thres], class_aware=False, matrix=self._matrix,
+                      status=self._status, count_all_fp=self.count_all_fp)
+
+    def process_batch(self, detections, labels) -> None:
+        """ONE image in the reference's layouts: detections (N, 6) x1, y1, x2, y2, conf, class; labels (M, 5) class, x1, y1, x2, y2 (device tensors)"""
+        import torch
+        det, lab = detections.detach().reshape(-1, 6), labels.detach().to(detections.device).reshape(-1, 5)
+        n, m = int(det.shape[0]), int(lab.shape[0])
+        slab = (det[None, :, :4], det[None, :, 4], det[None, :, 5].to(torch.int64), torch.full((1,), n, dtype=torch.int32, device=det.device))
+        self.update_from_slab(slab, (lab[None, :, 1:5].to(torch.float32), lab[None, :, 0].to(torch.int32), torch.full((1,), m, dtype=torch.int32, device=det.device)))
+
+    @property
+    def matrix(self) -> np.ndarray:
+        """(nc + 1, nc + 1) int64 on the host: one transfer; ValueError for a stale slab row, a label outside [0, nc) or a count above K"""
+        import torch
+        from ..ops import _raise_val_status
+        if self._matrix is None:
+            return np.zeros((self.nc + 1, self.nc + 1), np.int64)
+        both = torch.cat([self._status, self._matrix.view(-1)]).cpu().numpy()
+        _raise_val_status(int(both[1]))
+        return both[4:].reshape(self.nc + 1, self.nc + 1).astype(np.int64)
+
+
+class ValEvaluator:
+    """The statistics loop of YOLOv5's val.py on the MI355X: update() / update_from_slab() enqueue ONE ops.val_match launch per batch (class_aware=True, every
+    detection a candidate, pairs of IoU >= iouv[0] within a class, one-to-one by IoU) and keep the per-detection true-positive rows, scores, labels and the
+    ground-truth classes on the device -- no copy to the host, no synchronisation --; compute() makes one transfer and runs ap_per_class in float64.  At most 10
+    thresholds, 1024 detections and 1024 ground truths per image; no CPU fallback."""
+
+    def __init__(self, num_classes: int = 80, iouv=VAL_IOUV):
+        self.num_classes = int(num_classes)
+        self.iouv = [float(t) for t in iouv]
+        self._batches: List[tuple] = []   # per launch: (tp, scores, labels, counts, gt_labels, gt_counts) on the device
+        self._status = None
+
+    def update_from_slab(self, slab, targets) -> None:
+        """slab and targets as GpuDetectionEvaluator.update_from_slab takes them; one launch on the current stream, nothing read back"""
+        import torch
+        from .. import ops
+        boxes, scores, labels, counts = slab
+        n = int(scores.shape[0])
+        if not isinstance(targets, tuple) and len(targets) != n:
+            raise ValueError("one target per prediction is required")
+        if n == 0:
+            return
+        gb, gl, gc = GpuDetectionEvaluator._pad_targets(targets, boxes.device)
+        if self._status is None:
+            self._status = torch.zeros(4, device=boxes.device, dtype=torch.int32)
+        _, _, tp, _ = ops.val_match(boxes, scores, labels, counts, gb, gl, gc, self.num_classes, conf=float("-inf"), thrs=self.iouv, class_aware=True,
+                                    status=self._status)
+        # the slab's buffers are the caller's to reuse: keep copies of what compute() needs (device to device, on the same stream)
+        self._batches.append((tp, scores.detach().to(torch.float32, copy=True), labels.detach().to(torch.int32, copy=True), counts.detach().to(torch.int32, copy=True),
+                              gl.detach().to(torch.int32, copy=True), gc.detach().to(torch.int32, copy=True)))
+
+    def update(self, preds: Sequence[Dict], targets: Sequence[Dict]) -> None:
+        """preds: the model's List[Dict{boxes, scores, labels}] (device tensors); targets: List[Dict{boxes, labels}]: padded into a slab, then update_from_slab"""
+        if len(preds) != len(targets):
+            raise ValueError("one target per prediction is required")
+        if preds:
+            self.update_from_slab(_pad_preds(preds), targets)
+
+    def merge(self, other: "ValEvaluator") -> None:
+        """fold in another accumulator of the same device (ranks own disjoint image shards); no synchronisation"""
+        if other._status is None:
+            return
+        self._status = other._status.clone() if self._status is None else self._status | other._status
+        self._batches += other._batches
+
+    def compute(self) -> Dict:
+        """val.py's summary: mean precision / recall / F1 at the best-F1 confidence, map50, map (mean AP over iouv) over the classes that have ground truth, the
+        classes themselves (ap_class) and the per-class lists behind the means.  Zeros and empty lists when nothing can be scored (no true positive at iouv[0])."""
+        import torch
+        from ..ops import _raise_val_status
+        if not self._batches:
+            return val_summary(np.zeros((0, len(self.iouv))), np.zeros(0), np.zeros(0), np.zeros(0))
+        parts = [self._status] + [t for b in self._batches for t in b]   # ONE transfer: every buffer as bytes, concatenated on the device
+        flat = torch.cat([t.contiguous().view(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        arrays, off = [], 0
+        for t in parts:
+            nbytes = t.numel() * t.element_size()
+            arrays.append(flat[off: off + nbytes].view({torch.int32: np.int32, torch.uint8: np.uint8, torch.float32: np.float32}[t.dtype]).reshape(tuple(t.shape)))
+            off += nbytes
+        _raise_val_status(int(arrays[0][1]))
+        tps, conf, pcls, tcls = [], [], [], []
+        for b in range(len(self._batches)):
+            tp, sc, lab, cnt, gl, gc = arrays[1 + 6 * b: 7 + 6 * b]
+            live = np.arange(sc.shape[1])[None, :] < cnt[:, None]
+            tps.append(tp[live]); conf.append(sc[live]); pcls.append(lab[live])
+            tcls.append(gl[np.arange(gl.shape[1])[None, :] < gc[:, None]])
+        tps, conf, pcls, tcls = np.concatenate(tps), np.concatenate(conf), np.concatenate(pcls), np.concatenate(tcls)
+        return val_summary(tps, conf, pcls, tcls)
