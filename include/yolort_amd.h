@@ -621,6 +621,74 @@ typedef struct ymi_attn_desc {
 int ymi_attention(const ymi_attn_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * INT8 convolution with a requantising epilogue, and the quantise op that produces its input (post-training quantisation: symmetric, per-tensor activation scales,
+ * per-output-channel weight scales, no zero points).
+ *     y = requant(act(float(acc) * scale[co] + bias[co]) + res_scale * res)        acc = sum over taps and input channels of x * w, in int32
+ *   x        int8 NHWC view (n, h, w_in, cin), pixel stride x_cstride (>= cin, a multiple of 16), 16-byte aligned
+ *   w        the fragment-order blob of ymi_conv_i8_pack (below), 16-byte aligned;  scale, bias  fp32 [cout], 16-byte aligned
+ *   y        NHWC view (n, ho, wo, cout) of out_dtype YMI_I8, YMI_F16 or YMI_BF16, pixel stride y_cstride (>= cout, a multiple of 8), 8-byte aligned
+ *   res      optional view of y's shape AND TYPE, pixel stride res_cstride (>= cout, a multiple of 8), 8-byte aligned; NULL = none
+ *   k in {1, 3}, s in {1, 2}, p = k / 2, ho = (h + 2 p - k) / s + 1 (wo likewise);  cin % 16 == 0;  cout % 8 == 0;  act: all four YMI_ACT_* codes.
+ * THE ARITHMETIC (the contract), per output element:
+ *   1. acc is the EXACT int32 sum (v_mfma_i32_32x32x32_i8; integer addition is associative, so no order is part of the contract); out-of-image taps contribute 0.
+ *      |acc| <= 9 * cin * 127 * 127 must fit int32: cin <= 14784 at k = 3 (checked).
+ *   2. f = (float)acc: ONE conversion, round-to-nearest-even (it rounds only where |acc| > 2^24).
+ *   3. v = fmaf(f, scale[co], bias[co]): ONE fused multiply-add, one rounding.
+ *   4. v = act(v) in fp32: identity; SiLU as ymi_conv2d's epilogue computes it (v * rcp(1 + exp2(-v * log2 e)), the hardware exp2 / rcp, the 1/4-scaled form when
+ *      out_dtype is YMI_BF16); Hardswish / LeakyReLU(0.1) as ymi_act's (torch's order of operations).
+ *   5. with a shortcut: v = fmaf((float)res, res_scale, v), AFTER the activation, one fused multiply-add (int8 and 16-bit res convert to fp32 exactly; res_scale = 1
+ *      makes it a plain correctly rounded addition).
+ *   6. ONE final rounding.  YMI_F16 / YMI_BF16: round-to-nearest-even of v; out_scale is not read -- this is how a chain leaves the integer domain.
+ *      YMI_I8: q = rint(v * inv) with inv = 1.0f / out_scale computed ONCE on the host in fp32, ties to even, then clamped to [-127, 127]; NaN -> 0, +-inf -> +-127.
+ * conv_i8_kernel (csrc/conv_i8.hip) runs the product TRANSPOSED: output channels along the instruction's M, pixels along N, so that a lane's accumulators are runs of
+ * four consecutive output channels of one pixel (one 32-bit store of four int8 codes, or one 64-bit store of four 16-bit values).  A workgroup of four waves owns 128
+ * output pixels x a slab of up to 64 output channels; k = 3: an 8 x 16 spatial tile of one image whose input halo is staged in LDS 32 channels at a time (zeros outside
+ * the image), all nine taps reading it; k = 1: 128 consecutive pixels of the (n ho wo) raster, activations straight from memory to registers.  The weight slab streams
+ * through LDS, the next chunk's global loads in flight under the current chunk's MFMAs.  No atomics, no allocation, no synchronisation: ordered on `stream`, may be
+ * captured.  Nothing outside y's (n, ho, wo, cout) elements is written, nothing outside the (.., cin) / (.., cout) elements of x / res is read.
+ * YMI_EINVAL (nothing is launched; the message names ymi_conv2d_i8): a null descriptor or x / w / scale / bias / y, cin % 16 != 0, cout % 8 != 0, k / s / p outside the
+ * sets, a stride below its channel count or not a multiple of 16 (x) / 8 (y, res), out_dtype outside {I8, F16, BF16}, out_scale not finite or <= 0 for an int8 output,
+ * res_scale not finite, an unknown activation, a misaligned pointer, ho / wo that do not follow from h / w_in, n > 65535, n ho wo >= 2^31 - 128.  n == 0 is a no-op.
+ *
+ * THE WEIGHT BLOB.  With P = cin / 16 packets of 16 input channels per tap, P2 = P rounded up to even and CP = cout rounded up to 32, the blob is int8
+ * [k * k taps][P2][CP][16]: byte ((tap * P2 + p) * CP + co) * 16 + j holds w[co][16 p + j][ky][kx] of the OIHW tensor, tap = ky * k + kx, and 0 where p >= P or
+ * co >= cout.  One lane's weight operand of one matrix instruction is one aligned 16-byte read.  ymi_conv_i8_pack_bytes returns the blob's size (-1 for arguments
+ * ymi_conv2d_i8 would refuse); ymi_conv_i8_pack writes it: HOST code on HOST pointers, no device is touched.
+ *
+ * ymi_quantize_i8: y = clamp(rint(x * inv), -127, 127) with inv = 1.0f / scale computed once on the host in fp32; the product is one fp32 multiplication of the
+ * source converted to fp32 (exact for fp16 / bf16), rint rounds ties to even, NaN -> 0, +-inf -> +-127.  x: view (npix, c) of dtype YMI_F16 / YMI_BF16 / YMI_F32 with
+ * pixel stride x_cstride; y: int8 view, pixel stride y_cstride.  Any c >= 1 and strides >= c: a thread converts 16 channels with 16-byte accesses when c, both strides
+ * and both pointers are multiples of 16 elements, else one element (the scalar form).  YMI_EINVAL (the message names ymi_quantize_i8): null pointers, c < 1, npix < 0,
+ * a stride below c, a dtype outside the three, a scale that is not finite or <= 0, npix * c >= 2^39.
+ * ABI stays 6: two new structs, six new functions.
+ * ---------------------------------------------------------------------------------------- */
+#define YMI_I8 5 /* int8 storage: ymi_conv_i8_desc.out_dtype only */
+typedef struct ymi_conv_i8_desc {
+    const void* x;
+    const void* w;
+    const float* scale;
+    const float* bias;
+    void* y;
+    const void* res;
+    int32_t n, h, w_in, cin, x_cstride;
+    int32_t ho, wo, cout, y_cstride, res_cstride;
+    int32_t k, s, p;
+    int32_t act, out_dtype;
+    float out_scale, res_scale;
+} ymi_conv_i8_desc;
+int ymi_conv2d_i8(const ymi_conv_i8_desc* d, void* stream);
+int64_t ymi_conv_i8_pack_bytes(int cout, int cin, int k);
+int ymi_conv_i8_pack(const int8_t* w_oihw, int cout, int cin, int k, void* blob, int64_t blob_bytes);
+typedef struct ymi_quant_i8_desc {
+    const void* x;
+    void* y;
+    int32_t npix, c, x_cstride, y_cstride;
+    int32_t dtype;
+    float scale;
+} ymi_quant_i8_desc;
+int ymi_quantize_i8(const ymi_quant_i8_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Post-process (yolort/models/box_head.py:328-360,414-427 + torchvision batched_nms).
  * ymi_postprocess runs, on `stream`, with no host sync:
  *   1. decode   sigmoid, xy=(s*2-0.5+grid)*stride, wh=(s*2)^2*anchor (yolort/models/_utils.py:59-60,
@@ -999,6 +1067,10 @@ int ymi_plan_add_dwconv(ymi_plan* p, const ymi_dwconv_desc* d);
 /* ymi_attention as a plan op, on the same terms: checked here, captured, profiled, exported (q / k / v / o ride in the op record's convolution pointers x / w / bias /
  * y, the scale in its generic integer slot 0 as bits) */
 int ymi_plan_add_attention(ymi_plan* p, const ymi_attn_desc* d);
+/* ymi_conv2d_i8 / ymi_quantize_i8 as plan ops, on the same terms: checked here, captured, profiled, exported (x / w / bias / y / res in the op record's convolution
+ * pointers of those names and scale in its chain_bias; the quantise op's x / y in the record's generic pointers; the float fields in the integer slots as bits) */
+int ymi_plan_add_conv_i8(ymi_plan* p, const ymi_conv_i8_desc* d);
+int ymi_plan_add_quantize_i8(ymi_plan* p, const ymi_quant_i8_desc* d);
 int ymi_plan_num_ops(const ymi_plan* p);
 /* ymi_post_set_classes for every post-process descriptor recorded in the plan that carries YMI_POST_CLASS_FILTER (YMI_EINVAL if none does).  The plan remembers the
  * list: ymi_plan_export stores it, and ymi_plan_import writes the masks again before it returns, so an imported plan filters as the exporting one did; the consumer

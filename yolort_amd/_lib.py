@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("YOLORT_AMD_LIB") or os.path.join(_HERE, "lib", "libyo
 
 YMI_F16, YMI_BF16, YMI_F32, YMI_U8 = 0, 1, 2, 3
 YMI_U8_HWC = 4   # ymi_letterbox input only: interleaved (h, w, 3) uint8
+YMI_I8 = 5       # int8 storage: the output type of ymi_conv2d_i8 only
 ACT_NONE, ACT_SILU, ACT_HARDSWISH, ACT_LEAKY = 0, 1, 2, 3   # include/yolort_amd.h YMI_ACT_*: the last two belong to the legacy r3.1 blocks
 MAX_LEVELS = 4
 
@@ -255,6 +256,23 @@ class AttnDesc(C.Structure):
 ATTN_TILE = (64, 64)          # (YMI_ATTN_TILE_Q, YMI_ATTN_TILE_K): queries per workgroup, keys per LDS chunk
 ATTN_HEAD_DIMS = (32, 64, 128)
 
+
+class ConvI8Desc(C.Structure):
+    """ymi_conv_i8_desc: the views, the fragment-order weight blob, the fp32 epilogue vectors and the geometry of one int8 convolution (ymi_conv2d_i8)"""
+    _fields_ = [
+        ("x", C.c_void_p), ("w", C.c_void_p), ("scale", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("res", C.c_void_p),
+        ("n", C.c_int32), ("h", C.c_int32), ("w_in", C.c_int32), ("cin", C.c_int32), ("x_cstride", C.c_int32),
+        ("ho", C.c_int32), ("wo", C.c_int32), ("cout", C.c_int32), ("y_cstride", C.c_int32), ("res_cstride", C.c_int32),
+        ("k", C.c_int32), ("s", C.c_int32), ("p", C.c_int32), ("act", C.c_int32), ("out_dtype", C.c_int32), ("out_scale", C.c_float), ("res_scale", C.c_float),
+    ]
+
+
+class QuantI8Desc(C.Structure):
+    """ymi_quant_i8_desc: source view (npix, c) of dtype F16 / BF16 / F32, int8 destination view and the per-tensor scale of one quantise launch (ymi_quantize_i8)"""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("npix", C.c_int32), ("c", C.c_int32), ("x_cstride", C.c_int32), ("y_cstride", C.c_int32), ("dtype", C.c_int32), ("scale", C.c_float),
+    ]
+
 CLASSIFY_MAX_MAPS, CLASSIFY_MAX_K, CLASSIFY_LOGITS, CLASSIFY_HIDDEN_LOGITS = 4, 2496, 0, 1   # YMI_CLASSIFY_*
 FILTER_STATUS_BAD_COUNT, FILTER_STATUS_TOTAL, FILTER_STATUS_CAPACITY, FILTER_MAX_K = 1, 2, 4, 32768   # YMI_FILTER_*
 
@@ -343,6 +361,12 @@ _SIGS = {
     "ymi_plan_add_dwconv": (C.c_int, [C.c_void_p, C.POINTER(DwConvDesc)]),
     "ymi_attention": (C.c_int, [C.POINTER(AttnDesc), C.c_void_p]),
     "ymi_plan_add_attention": (C.c_int, [C.c_void_p, C.POINTER(AttnDesc)]),
+    "ymi_conv2d_i8": (C.c_int, [C.POINTER(ConvI8Desc), C.c_void_p]),
+    "ymi_plan_add_conv_i8": (C.c_int, [C.c_void_p, C.POINTER(ConvI8Desc)]),
+    "ymi_quantize_i8": (C.c_int, [C.POINTER(QuantI8Desc), C.c_void_p]),
+    "ymi_plan_add_quantize_i8": (C.c_int, [C.c_void_p, C.POINTER(QuantI8Desc)]),
+    "ymi_conv_i8_pack_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "ymi_conv_i8_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "ymi_plan_create": (C.c_void_p, []),
     "ymi_plan_destroy": (None, [C.c_void_p]),
     "ymi_plan_add_conv": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc)]),
@@ -428,7 +452,7 @@ def normalize_classes(classes, num_classes: Optional[int] = None):
 
 def dtype_code(dt: torch.dtype) -> int:
     try:
-        return {torch.float16: YMI_F16, torch.bfloat16: YMI_BF16, torch.float32: YMI_F32, torch.uint8: YMI_U8}[dt]
+        return {torch.float16: YMI_F16, torch.bfloat16: YMI_BF16, torch.float32: YMI_F32, torch.uint8: YMI_U8, torch.int8: YMI_I8}[dt]
     except KeyError:
         raise YmiError(f"unsupported dtype {dt}") from None
 

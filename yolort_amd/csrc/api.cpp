@@ -66,8 +66,12 @@ int dwconv_check(const ymi_dwconv_desc* d);
 int dwconv_launch(const ymi_dwconv_desc* d, hipStream_t s);
 int attention_check(const ymi_attn_desc* d);
 int attention_launch(const ymi_attn_desc* d, hipStream_t s);
+int conv_i8_check(const ymi_conv_i8_desc* d);
+int conv_i8_launch(const ymi_conv_i8_desc* d, hipStream_t s);
+int quantize_i8_check(const ymi_quant_i8_desc* d);
+int quantize_i8_launch(const ymi_quant_i8_desc* d, hipStream_t s);
 
-enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW, OP_DWCONV, OP_ATTENTION };
+enum OpKind { OP_CONV, OP_SPP, OP_UP, OP_COPY, OP_POST, OP_POST_BEGIN, OP_HEAD_DECODE, OP_HEAD_GROUP, OP_POST_FINISH, OP_C3_FUSED, OP_ACT, OP_SCALE_VIEW, OP_POST_VIEW, OP_DWCONV, OP_ATTENTION, OP_CONV_I8, OP_QUANT_I8 };
 
 struct Op {
     OpKind kind;
@@ -104,6 +108,25 @@ static ymi_attn_desc attn_of(const Op& op) {
     return d;
 }
 
+// OP_CONV_I8 likewise: x / w / bias / y / res in the fields of those names, scale in chain_bias (all relocated), cin = cin, kh = k, sh = s, ph = p, out_dtype; the bits
+// of out_scale / res_scale in i[0] / i[1].  OP_QUANT_I8: x / y in the generic pointers, npix / c / strides / dtype in i[0 .. 4], the scale's bits in i[5].
+static ymi_conv_i8_desc conv_i8_of(const Op& op) {
+    const ymi_conv_desc& c = op.conv;
+    ymi_conv_i8_desc d;
+    d.x = c.x; d.w = c.w; d.scale = c.chain_bias; d.bias = c.bias; d.y = c.y; d.res = c.res;
+    d.n = c.n; d.h = c.h; d.w_in = c.w_in; d.cin = c.cin; d.x_cstride = c.x_cstride; d.ho = c.ho; d.wo = c.wo; d.cout = c.cout; d.y_cstride = c.y_cstride; d.res_cstride = c.res_cstride;
+    d.k = c.kh; d.s = c.sh; d.p = c.ph; d.act = c.act; d.out_dtype = c.out_dtype;
+    memcpy(&d.out_scale, &op.i[0], sizeof(float));
+    memcpy(&d.res_scale, &op.i[1], sizeof(float));
+    return d;
+}
+static ymi_quant_i8_desc quant_i8_of(const Op& op) {
+    ymi_quant_i8_desc d;
+    d.x = op.x; d.y = op.y; d.npix = op.i[0]; d.c = op.i[1]; d.x_cstride = op.i[2]; d.y_cstride = op.i[3]; d.dtype = op.i[4];
+    memcpy(&d.scale, &op.i[5], sizeof(float));
+    return d;
+}
+
 static int run_op(const Op& op, hipStream_t s) {
     switch (op.kind) {
         case OP_CONV: return conv2d_launch(&op.conv, s);
@@ -126,6 +149,14 @@ static int run_op(const Op& op, hipStream_t s) {
         case OP_ATTENTION: {
             const ymi_attn_desc d = attn_of(op);
             return attention_launch(&d, s);
+        }
+        case OP_CONV_I8: {
+            const ymi_conv_i8_desc d = conv_i8_of(op);
+            return conv_i8_launch(&d, s);
+        }
+        case OP_QUANT_I8: {
+            const ymi_quant_i8_desc d = quant_i8_of(op);
+            return quantize_i8_launch(&d, s);
         }
     }
     set_error("unknown op kind");
@@ -388,6 +419,37 @@ extern "C" int ymi_plan_add_attention(ymi_plan* p, const ymi_attn_desc* d) {
     c.n = d->n; c.h = d->S; c.w_in = d->heads; c.cin = d->d; c.cout = d->c;
     c.x_cstride = d->q_cstride; c.res_cstride = d->k_cstride; c.y2_cstride = d->v_cstride; c.y_cstride = d->o_cstride; c.dtype = d->dtype;
     memcpy(&op.i[0], &d->scale, sizeof(float));
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
+extern "C" int ymi_plan_add_conv_i8(ymi_plan* p, const ymi_conv_i8_desc* d) {
+    YMI_REQUIRE(p && d, "ymi_plan_add_conv_i8: null argument");
+    if (const int rc = conv_i8_check(d)) return rc;
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_CONV_I8;
+    ymi_conv_desc& c = op.conv;
+    c.x = d->x; c.w = d->w; c.chain_bias = d->scale; c.bias = d->bias; c.y = d->y; c.res = d->res;
+    c.n = d->n; c.h = d->h; c.w_in = d->w_in; c.cin = d->cin; c.x_cstride = d->x_cstride; c.ho = d->ho; c.wo = d->wo; c.cout = d->cout; c.y_cstride = d->y_cstride; c.res_cstride = d->res_cstride;
+    c.kh = d->k; c.sh = d->s; c.ph = d->p; c.act = d->act; c.out_dtype = d->out_dtype;
+    memcpy(&op.i[0], &d->out_scale, sizeof(float));
+    memcpy(&op.i[1], &d->res_scale, sizeof(float));
+    p->ops.push_back(op);
+    drop_graph(p);
+    return (int)p->ops.size() - 1;
+}
+
+extern "C" int ymi_plan_add_quantize_i8(ymi_plan* p, const ymi_quant_i8_desc* d) {
+    YMI_REQUIRE(p && d, "ymi_plan_add_quantize_i8: null argument");
+    if (const int rc = quantize_i8_check(d)) return rc;
+    Op op;
+    memset(&op, 0, sizeof(op));
+    op.kind = OP_QUANT_I8;
+    op.x = d->x; op.y = d->y;
+    op.i[0] = d->npix; op.i[1] = d->c; op.i[2] = d->x_cstride; op.i[3] = d->y_cstride; op.i[4] = d->dtype;
+    memcpy(&op.i[5], &d->scale, sizeof(float));
     p->ops.push_back(op);
     drop_graph(p);
     return (int)p->ops.size() - 1;

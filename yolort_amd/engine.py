@@ -152,6 +152,57 @@ def fold_linear(chains: Sequence[Sequence[Tensor]], bias: Optional[Tensor], dtyp
     return PackedConv(torch.cat(rows).to(dtype)[:, :, None, None], bias, None, dtype, device)
 
 
+class PackedConvI8:
+    """Weights of one INT8 convolution (ymi_conv2d_i8, csrc/conv_i8.hip).  BatchNorm is folded with PackedConv's formula in float64; the folded weights are quantised
+    symmetrically per output channel -- w_scale[co] = max|w[co]| / 127 (1 where the row is all zero), wq = clamp(rint(w / w_scale), +-127) -- and packed in the
+    kernel's fragment order by ymi_conv_i8_pack.  `in_scale` is the per-tensor scale of the int8 input: the epilogue multiplies the int32 sum by
+    scale[co] = fp32(in_scale * w_scale[co]) and adds the fp32 bias.  Attributes: wq (int8 OIHW), w_scale (float64), scale / bias (fp32, on the device), w (the blob)."""
+
+    def __init__(self, weight: Tensor, bias: Optional[Tensor], bn: Optional[Tuple[Tensor, Tensor, Tensor, Tensor, float]], in_scale: float, device: torch.device):
+        w = weight.detach().to(device="cpu", dtype=torch.float64)
+        cout = w.shape[0]
+        b = torch.zeros(cout, dtype=torch.float64) if bias is None else bias.detach().to(device="cpu", dtype=torch.float64)
+        if bn is not None:
+            g, beta, mean, var, eps = bn
+            scale = g.detach().double().cpu() / torch.sqrt(var.detach().double().cpu() + eps)
+            w = w * scale.view(-1, 1, 1, 1)
+            b = beta.detach().double().cpu() + (b - mean.detach().double().cpu()) * scale
+        amax = w.abs().amax(dim=(1, 2, 3))
+        self.w_folded = w
+        self.w_scale = torch.where(amax > 0, amax / 127.0, torch.ones_like(amax))
+        self.wq = torch.clamp(torch.round(w / self.w_scale.view(-1, 1, 1, 1)), -127, 127).to(torch.int8).contiguous()
+        self.bias64, self.in_scale = b, float(in_scale)
+        self._pack(device)
+
+    @classmethod
+    def from_quantized(cls, wq: Tensor, w_scale: Tensor, bias: Tensor, in_scale: float, device: torch.device) -> "PackedConvI8":
+        """from weights that are already int8 codes (a quantised state_dict): wq (cout, cin, k, k) int8, w_scale and bias (cout)"""
+        self = cls.__new__(cls)
+        self.w_folded = None
+        self.wq, self.w_scale = wq.detach().to(device="cpu", dtype=torch.int8).contiguous(), w_scale.detach().to(device="cpu", dtype=torch.float64)
+        self.bias64, self.in_scale = bias.detach().to(device="cpu", dtype=torch.float64), float(in_scale)
+        self._pack(device)
+        return self
+
+    def _pack(self, device: torch.device) -> None:
+        cout, cin, kh, kw = self.wq.shape
+        if kh != kw:
+            raise YmiError(f"int8 convolution weights must be (cout, cin, k, k), got {tuple(self.wq.shape)}")
+        if not 0.0 < self.in_scale < float("inf"):
+            raise YmiError(f"in_scale must be finite and > 0, got {self.in_scale}")
+        self.cout, self.cin, self.k = cout, cin, kh
+        lib = _lib.load()
+        nbytes = lib.ymi_conv_i8_pack_bytes(cout, cin, kh)
+        if nbytes < 0:
+            raise YmiError(f"the int8 convolution needs cin % 16 == 0, cout % 8 == 0 and k in {{1, 3}} (got cin {cin}, cout {cout}, k {kh})")
+        blob = torch.empty(nbytes, dtype=torch.int8)
+        check(lib.ymi_conv_i8_pack(self.wq.data_ptr(), cout, cin, kh, blob.data_ptr(), nbytes), "ymi_conv_i8_pack")
+        self.w = blob.to(device)
+        self.scale = (self.in_scale * self.w_scale).to(torch.float32).to(device).contiguous()
+        self.bias = self.bias64.to(torch.float32).to(device).contiguous()
+        self._ktabs: Dict[Tuple[int, int], Tensor] = {}   # (none: Plan.export walks packed weights of every kind alike)
+
+
 _TILE_TABLE: Optional[Dict[str, int]] = None
 TILE_TABLE_PATH = os.environ.get("YOLORT_AMD_TILE_TABLE_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "tiles_gfx950.json")   # override: A/B runs only
 
@@ -458,6 +509,52 @@ class Plan:
         self.io[self.num_ops] = {"name": name, "x": q, "k": k, "v": v, "y": out, "res": None}
         self._record(self.lib.ymi_plan_add_attention(self.handle, C.byref(d)), name, kind="attention", flops=4.0 * q.n * heads * d.S * d.S * d.d,
                      bytes=float(4 * q.n * d.S * q.c * out.base.element_size()), shape=f"attn{q.c} h{heads} d{d.d} {q.h}x{q.w}")
+        return out
+
+    def quantize_i8(self, x: View, scale: float, out: Optional[View] = None, name: str = "quantize_i8") -> View:
+        """q = clamp(rint(x / scale), +-127) of a 16-bit / fp32 view into an int8 view (ymi_quantize_i8, csrc/conv_i8.hip): the input of a chain of int8 convolutions."""
+        if self.fp32:
+            raise YmiError(f"{name}: the fp32 parity mode has no int8 path (compute in float16 or bfloat16)")
+        if out is None:
+            out = self.alloc(x.n, x.h, x.w, x.c, torch.int8)
+        if (out.n, out.h, out.w, out.c) != (x.n, x.h, x.w, x.c) or out.dtype != torch.int8:
+            raise YmiError(f"{name}: the output must be an int8 view of the input's shape")
+        d = _lib.QuantI8Desc(x=x.ptr, y=out.ptr, npix=x.n * x.h * x.w, c=x.c, x_cstride=x.cs, y_cstride=out.cs, dtype=dtype_code(x.dtype), scale=float(scale))
+        self.keep.append(d)
+        self.io[self.num_ops] = {"name": name, "x": x, "y": out, "res": None}
+        self._record(self.lib.ymi_plan_add_quantize_i8(self.handle, C.byref(d)), name, kind="quantize_i8", flops=0.0,
+                     bytes=float(d.npix * x.c * (x.base.element_size() + 1)), shape=f"q{x.c} {x.h}x{x.w}")
+        return out
+
+    def conv_i8(self, x: View, pc: PackedConvI8, stride: int = 1, act: int = ACT_SILU, out_scale: Optional[float] = None, out: Optional[View] = None,
+                res: Optional[View] = None, res_scale: float = 1.0, name: str = "conv_i8") -> View:
+        """y = requant(act(acc * scale + bias) + res_scale * res) on the i8 matrix instruction (ymi_conv2d_i8, csrc/conv_i8.hip; the arithmetic is the contract in
+        include/yolort_amd.h): k in {1, 3}, stride 1 / 2, pad k // 2.  With `out_scale` the result is an int8 view (the chain stays in the integer domain); without
+        it a view of the plan's 16-bit dtype.  `res` has the output's type.  `x`, `out` and `res` may be channel slices of wider buffers."""
+        if self.fp32:
+            raise YmiError(f"{name}: the fp32 parity mode has no int8 path (compute in float16 or bfloat16)")
+        if x.dtype != torch.int8 or x.c != pc.cin:
+            raise YmiError(f"{name}: the input must be an int8 view of {pc.cin} channels (got {x.dtype}, {x.c}); Plan.quantize_i8 makes one")
+        odt = torch.int8 if out_scale is not None else self.dtype
+        ho, wo = conv_out_hw(x.h, x.w, (pc.k, pc.k), (stride, stride), (pc.k // 2, pc.k // 2))
+        if out is None:
+            out = self.alloc(x.n, ho, wo, pc.cout, odt)
+        if (out.n, out.h, out.w, out.c) != (x.n, ho, wo, pc.cout) or out.dtype != odt:
+            raise YmiError(f"{name}: output view {(out.n, out.h, out.w, out.c)} of {out.dtype} != expected {(x.n, ho, wo, pc.cout)} of {odt}")
+        if res is not None and ((res.n, res.h, res.w, res.c) != (out.n, out.h, out.w, out.c) or res.dtype != odt):
+            raise YmiError(f"{name}: the shortcut view must match the output's shape and type")
+        d = _lib.ConvI8Desc()
+        d.x, d.w, d.scale, d.bias, d.y, d.res = x.ptr, pc.w.data_ptr(), pc.scale.data_ptr(), pc.bias.data_ptr(), out.ptr, None if res is None else res.ptr
+        d.n, d.h, d.w_in, d.cin, d.x_cstride = x.n, x.h, x.w, pc.cin, x.cs
+        d.ho, d.wo, d.cout, d.y_cstride, d.res_cstride = ho, wo, pc.cout, out.cs, 0 if res is None else res.cs
+        d.k, d.s, d.p, d.act, d.out_dtype = pc.k, stride, pc.k // 2, act, dtype_code(odt)
+        d.out_scale, d.res_scale = 0.0 if out_scale is None else float(out_scale), float(res_scale)
+        self.keep.extend([pc, d])
+        self.io[self.num_ops] = {"name": name, "x": x, "y": out, "res": res, "stride": (stride, stride), "pad": (pc.k // 2, pc.k // 2)}
+        osz = out.base.element_size()
+        self._record(self.lib.ymi_plan_add_conv_i8(self.handle, C.byref(d)), name, kind="conv_i8", flops=2.0 * x.n * ho * wo * pc.cout * pc.cin * pc.k * pc.k,
+                     bytes=float(x.n * x.h * x.w * pc.cin + x.n * ho * wo * pc.cout * osz * (2 if res is not None else 1) + pc.w.numel() + 8 * pc.cout),
+                     shape=f"i8 {pc.cin}->{pc.cout} k{pc.k} s{stride} {x.h}x{x.w}->{ho}x{wo}")
         return out
 
     def _pinned_ok(self, d: ConvDesc, tile: int) -> bool:
@@ -918,9 +1015,10 @@ class Plan:
         def walk(o):
             if isinstance(o, Tensor):
                 add(o, REGION_SCRATCH)
-            elif isinstance(o, (PackedConv, PackedDWConv)):
+            elif isinstance(o, (PackedConv, PackedDWConv, PackedConvI8)):
                 add(o.w, REGION_CONST)
                 add(o.bias, REGION_CONST)
+                add(getattr(o, "scale", None), REGION_CONST)
                 for kt in o._ktabs.values():
                     add(kt, REGION_CONST)
             elif isinstance(o, PostBuffers):

@@ -841,3 +841,66 @@ def attention(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: Optional[float
     with torch.cuda.device(q.device):
         check(lib.ymi_attention(C.byref(d), _lib.stream_ptr()), "ymi_attention")
     return out
+
+
+def _nhwc_of(t: Tensor, align: int):
+    """(the (n, h, w, c) view of an NCHW tensor, its pixel stride): read in place when the memory already is one NHWC view (channels_last, or a channel slice of
+    one) with a 16-byte aligned start and a pixel stride that is a multiple of `align`; copied once otherwise"""
+    v = t.detach().permute(0, 2, 3, 1)
+    n, h, w, c = v.shape
+    cs = v.stride(2)
+    if v.numel() == 0 or not (v.stride(3) == 1 and cs >= c and cs % align == 0 and v.stride(1) == w * cs and v.stride(0) == h * w * cs and v.data_ptr() % 16 == 0):
+        v, cs = v.contiguous(), c
+    return v, cs
+
+
+def quantize_int8(x: Tensor, scale: float) -> Tensor:
+    """q = clamp(rint(x / scale), -127, 127) as int8: the per-tensor symmetric quantisation that feeds conv2d_int8 (ymi_quantize_i8, csrc/conv_i8.hip; NaN -> 0, ties
+    to even).  x: float16 / bfloat16 / float32 NCHW device tensor.  Returns an int8 NCHW tensor in channels_last memory (the NHWC layout the convolution reads in
+    place).  One launch on the current stream (a source that is not channels_last is first copied into that layout by torch); no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    if not x.is_cuda:
+        raise YmiError("quantize_int8 runs on an MI355X only (no CPU fallback)")
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise YmiError(f"quantize_int8: a float16 / bfloat16 / float32 NCHW tensor is needed, got {x.dtype} {tuple(x.shape)}")
+    xv, xcs = _nhwc_of(x, 1)
+    n, h, w, c = xv.shape
+    out = torch.empty((n, h, w, c), device=x.device, dtype=torch.int8)
+    d = _lib.QuantI8Desc(x=xv.data_ptr(), y=out.data_ptr(), npix=n * h * w, c=c, x_cstride=xcs, y_cstride=c,
+                         dtype=_lib.dtype_code(x.dtype), scale=float(scale))
+    with torch.cuda.device(x.device):
+        check(lib.ymi_quantize_i8(C.byref(d), _lib.stream_ptr()), "ymi_quantize_i8")
+    return out.permute(0, 3, 1, 2)
+
+
+def conv2d_int8(xq: Tensor, packed, stride: int = 1, act: int = _lib.ACT_SILU, out_scale: Optional[float] = None, res: Optional[Tensor] = None, res_scale: float = 1.0,
+                dtype: torch.dtype = torch.float16) -> Tensor:
+    """INT8 convolution with the requantising epilogue y = requant(act(acc * scale + bias) + res_scale * res) (ymi_conv2d_i8, csrc/conv_i8.hip; the arithmetic is the
+    contract in include/yolort_amd.h).  xq: int8 NCHW device tensor (quantize_int8 makes one); packed: engine.PackedConvI8 (k in {1, 3}, padding k // 2); stride 1 / 2;
+    act: an _lib.ACT_* code.  With `out_scale` the result is int8 (codes of y / out_scale), else `dtype` (float16 / bfloat16); `res` is an NCHW tensor of the result's
+    shape and type.  Returns an NCHW tensor in channels_last memory.  One launch on the current stream; no CPU fallback."""
+    lib = _lib.load(require_gpu=True)
+    if not xq.is_cuda:
+        raise YmiError("conv2d_int8 runs on an MI355X only (no CPU fallback)")
+    if xq.dim() != 4 or xq.dtype != torch.int8 or xq.shape[1] != packed.cin:
+        raise YmiError(f"conv2d_int8: an int8 NCHW tensor of {packed.cin} channels is needed, got {xq.dtype} {tuple(xq.shape)}")
+    odt = torch.int8 if out_scale is not None else dtype
+    if odt not in (torch.int8, torch.float16, torch.bfloat16):
+        raise YmiError(f"conv2d_int8: the output is int8 (with out_scale), float16 or bfloat16, got {odt}")
+    xv, xcs = _nhwc_of(xq, 16)
+    n, h, w, _ = xv.shape
+    k = packed.k
+    ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (w + 2 * (k // 2) - k) // stride + 1
+    out = torch.empty((n, ho, wo, packed.cout), device=xq.device, dtype=odt)
+    rv, rcs = None, 0
+    if res is not None:
+        if tuple(res.shape) != (n, packed.cout, ho, wo) or res.dtype != odt:
+            raise YmiError(f"conv2d_int8: the shortcut must be {(n, packed.cout, ho, wo)} of {odt}, got {tuple(res.shape)} of {res.dtype}")
+        rv, rcs = _nhwc_of(res, 8)
+    d = _lib.ConvI8Desc(x=xv.data_ptr(), w=packed.w.data_ptr(), scale=packed.scale.data_ptr(), bias=packed.bias.data_ptr(), y=out.data_ptr(), res=None if rv is None else rv.data_ptr(),
+                        n=n, h=h, w_in=w, cin=packed.cin, x_cstride=xcs, ho=ho, wo=wo, cout=packed.cout, y_cstride=packed.cout,
+                        res_cstride=rcs, k=k, s=stride, p=k // 2, act=act, out_dtype=_lib.dtype_code(odt),
+                        out_scale=0.0 if out_scale is None else float(out_scale), res_scale=float(res_scale))
+    with torch.cuda.device(xq.device):
+        check(lib.ymi_conv2d_i8(C.byref(d), _lib.stream_ptr()), "ymi_conv2d_i8")
+    return out.permute(0, 3, 1, 2)

@@ -18,10 +18,10 @@ import torch
 from torch import nn
 
 from ..._lib import ACT_HARDSWISH, ACT_LEAKY, ACT_NONE, ACT_SILU, YmiError
-from ...engine import PackedConv, PackedDWConv, Plan, View, fold_linear
-from ...hipmodule import HipModule
+from ...engine import PackedConv, PackedConvI8, PackedDWConv, Plan, View, fold_linear
+from ...hipmodule import HipModule, view_to_nchw as _view_to_nchw
 
-__all__ = ["Conv", "DWConv", "Bottleneck", "BottleneckCSP", "C3", "C3Ghost", "GhostConv", "GhostBottleneck", "SPP", "SPPF", "Focus", "Classify", "TransformerLayer", "TransformerBlock",
+__all__ = ["Conv", "DWConv", "QConv", "Bottleneck", "BottleneckCSP", "C3", "C3Ghost", "GhostConv", "GhostBottleneck", "SPP", "SPPF", "Focus", "Classify", "TransformerLayer", "TransformerBlock",
            "C3TR", "autopad", "focus_transform", "space_to_depth"]
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.03  # set after construction by the reference (darknetv6.py:110-112)
@@ -105,6 +105,69 @@ class DWConv(Conv):
         if c1 != c2 or k not in (3, 5):
             raise NotImplementedError(f"DWConv is implemented for c1 == c2 (no channel multiplier, no partial groups) and k in {{3, 5}}, got c1 = {c1}, c2 = {c2}, k = {k}")
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), act=act, version=version)
+
+
+class QConv(HipModule):
+    """A Conv quantised after training: int8 activations and weights on the i8 matrix instruction, the folded BatchNorm, the activation, the shortcut and the
+    requantisation in the epilogue (ymi_conv2d_i8, csrc/conv_i8.hip).  Built with QConv.from_float(conv, in_scale, out_scale) from an eval-mode Conv: symmetric
+    per-output-channel weight scales (engine.PackedConvI8), one scale for the input tensor and one for the output.  With `out_scale` the block emits int8, so chains of
+    QConv stay in the integer domain; with out_scale = None it emits the plan's 16-bit dtype and ends the chain.  g == 1, k in {1, 3}, stride in {1, 2}; anything else
+    raises NotImplementedError.  The state_dict holds wq (int8 OIHW), w_scale, bias, in_scale and out_scale (0 = none) as buffers.  Picking the scales
+    (calibration) is the caller's business."""
+
+    def __init__(self, c1, c2, k=1, s=1, act=ACT_SILU):
+        super().__init__()
+        if k not in (1, 3) or s not in (1, 2):
+            raise NotImplementedError(f"the int8 kernel implements k in {{1, 3}}, s in {{1, 2}} and padding k // 2 (got k = {k}, s = {s})")
+        if c1 % 16 or c2 % 8:
+            raise NotImplementedError(f"the int8 kernel needs c1 % 16 == 0 and c2 % 8 == 0 (got {c1} -> {c2})")
+        self.k, self.s, self.act_code = k, s, act
+        self.register_buffer("wq", torch.zeros(c2, c1, k, k, dtype=torch.int8))
+        self.register_buffer("w_scale", torch.ones(c2, dtype=torch.float64))
+        self.register_buffer("bias", torch.zeros(c2, dtype=torch.float32))
+        self.register_buffer("in_scale", torch.ones((), dtype=torch.float64))
+        self.register_buffer("out_scale", torch.zeros((), dtype=torch.float64))
+        self._packed: Dict[Tuple, Tuple] = {}
+
+    @classmethod
+    def from_float(cls, conv: Conv, in_scale: float, out_scale: Optional[float] = None) -> "QConv":
+        if not isinstance(conv, Conv) or conv.training:
+            raise NotImplementedError("QConv.from_float takes a Conv in eval mode (BatchNorm is folded from its running statistics)")
+        c = conv.conv
+        k, s = c.kernel_size[0], c.stride[0]
+        if c.groups != 1 or c.kernel_size != (k, k) or c.stride != (s, s) or c.padding != (k // 2, k // 2):
+            raise NotImplementedError(f"the int8 kernel implements g = 1, square k in {{1, 3}} and padding k // 2 (got g = {c.groups}, k = {c.kernel_size}, p = {c.padding})")
+        q = cls(c.in_channels, c.out_channels, k, s, act_code(conv.act))
+        bn = (conv.bn.weight, conv.bn.bias, conv.bn.running_mean, conv.bn.running_var, float(conv.bn.eps))
+        pc = PackedConvI8(c.weight, None, bn, in_scale, torch.device("cpu"))
+        q.wq.copy_(pc.wq)
+        q.w_scale.copy_(pc.w_scale)
+        q.bias.copy_(pc.bias)
+        q.in_scale.fill_(float(in_scale))
+        q.out_scale.fill_(0.0 if out_scale is None else float(out_scale))
+        return q.to(c.weight.device).eval()
+
+    def packed(self, device: torch.device) -> PackedConvI8:
+        sig = tuple(t._version for t in (self.wq, self.w_scale, self.bias, self.in_scale)) + (self.wq.data_ptr(),)
+        hit = self._packed.get(device)
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        pc = PackedConvI8.from_quantized(self.wq, self.w_scale, self.bias, float(self.in_scale), device)
+        self._packed[device] = (sig, pc)
+        return pc
+
+    def emit(self, plan: Plan, x: View, out: Optional[View] = None, res: Optional[View] = None, res_scale: float = 1.0, name: str = "qconv") -> View:
+        """`x`: an int8 view (codes of value / in_scale); a 16-bit view -- the edge of forward() -- is quantised with in_scale first"""
+        if x.dtype != torch.int8:
+            x = plan.quantize_i8(x, float(self.in_scale), name=name + ".quantize")
+        osc = float(self.out_scale)
+        return plan.conv_i8(x, self.packed(plan.device), self.s, self.act_code, out_scale=osc if osc > 0.0 else None, out=out, res=res, res_scale=res_scale, name=name)
+
+    def _forward_on_device(self, xs, is_list):
+        y = self._run_plan(xs, is_list)
+        if y.dtype == torch.int8:   # the codes, NCHW
+            return y.as_tensor().permute(0, 3, 1, 2).contiguous()
+        return _view_to_nchw(y, xs[0].dtype)
 
 
 class GhostConv(HipModule):
