@@ -468,7 +468,32 @@ int ymi_conv_build_ktab(int cin, int kh, int kw, int w_in, int x_cstride, int k_
 /* fp32 mode (dtype = out_dtype = YMI_F32: fp32 activations and weights, exact fp32 arithmetic on the f32-input MFMA -- the
  * arithmetic of the reference's CPU path, common.py:69-70 run in torch.float32): the tile ymi_conv2d takes for tile == 0,
  * a function of (n*ho*wo, cout_pad) only, so every process sums in the same order.  Tiles 201-206 are the LDS-DMA
- * pipelined kernels (need desc.zeros); a negative tile id selects the register-staged kernel of rounds 2-4. */
+ * pipelined kernels (need desc.zeros); a negative tile id selects the register-staged kernel of rounds 2-4.
+ *
+ * fp32 mode on the 16-bit matrix pipe (csrc/conv_f32_split.hip; opt-in by tile id, never chosen for tile == 0): tiles 211-216 are the geometries of
+ * 201-206 with NP = 6 bf16 products per k, 221-226 the same with NP = 8.  Same descriptor, same fp32 storage and packing, same epilogue; accepted for
+ * YMI_F32 descriptors with desc.zeros only, and only where the matching 20x tile accepts the shape -- everything else is YMI_EINVAL.
+ * THE ARITHMETIC (the contract).  Every fp32 operand v is split in registers, round-to-nearest-even, into three bf16 terms
+ *     hi = bf16(v),  mid = bf16(v - hi),  lo = bf16(v - hi - mid).
+ *   With 2^e <= |v| < 2^(e+1): |v - hi| <= 2^(e-8) (half a bf16 ulp) and v - hi is a multiple of 2^(e-23), so it has at most 16 significant bits and the
+ *   subtraction is exact in fp32; |mid| <= 2^(e-8) <= 2^-8 |v|; |v - hi - mid| <= 2^(e-16), again a multiple of 2^(e-23): at most 8 significant bits, the
+ *   second subtraction is exact, lo holds it exactly, |lo| <= 2^-16 |v|, and hi + mid + lo == v.  This holds for finite v with 2^-100 <= |v| < 2^127
+ *   (below, lo may be flushed; above, hi may round to infinity) and for v = 0; non-finite operands propagate as NaN / Inf and are not claimed.
+ *   Products: x . w = sum over the 9 pairs of terms.  NP = 8 issues all but lo.lo; NP = 6 also omits lo.mid and mid.lo.  Per product of an output
+ *     dropped <= D_NP |x||w|,   D_6 = 2 * 2^-8 * 2^-16 + 2^-32 = 2^-23 + 2^-32,   D_8 = 2^-32.
+ *   Each issued bf16 x bf16 product is exact in fp32 (16 significant bits); their magnitudes sum to at most (|hi| + |mid| + |lo|)_x (...)_w <=
+ *   (1 + 2^-7 + 2^-16)^2 |x||w| <= 1.016 |x||w|.  They are accumulated in fp32 by v_mfma_f32_32x32x16_bf16, smallest products first, 64 k per partial sum,
+ *   the partial sums folded every four 16-deep steps like tiles 201-206, then + the fp32 bias.  A term passes through at most
+ *     n = 64 * NP + ceil(k_pad / 64) + 1
+ *   rounded additions (one per product of its partial sum if the instruction rounded after every product -- its internal order is not documented --, the
+ *   fold, the bias).  The worst case n * 2^-24 is 2^-15.4 for NP = 6: larger than the 2^-16 a kernel that dropped `lo` altogether would be off by, so a bound
+ *   of that kind checks nothing.  The contract is the probabilistic one (Higham and Mary, SIAM J. Sci. Comput. 41 (2019), theorem 2.4, lambda = 6:
+ *   for rounding errors of mean zero it fails for one output with probability below 4e-8):
+ *     A_NP = 6 * sqrt(n) * 2^-24 * 1.016
+ *     |pre-activation - exact| <= D_NP * S + A_NP * (S + |bias|),   S = sum over the output's K products of |x||w|, exact = sum x w + bias.
+ *   (NP = 6, K = 144: D = 1.19e-7, A = 7.2e-6.)  The activation, the shortcut and the stores are those of tiles 201-206: SiLU as v / (1 + expf(-v)), |SiLU'| <= 1.1,
+ *   within 2 ulp of fp32 of its own argument; the shortcut added after it with one more rounding.
+ *   Bf16-representable operands have mid = lo = 0: with exact sums (below 2^24 in units of the smallest product) the output equals tile 20x bit for bit. */
 int ymi_conv_f32_pick_tile(int m_pixels, int cout_pad);
 
 /* ------------------------------------------------------------------------------------------

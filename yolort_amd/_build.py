@@ -13,7 +13,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.environ.get("YOLORT_AMD_BUILD_OUT") or os.path.join(LIBDIR, "libyolort_amd.so")   # override: tuning builds only
-SOURCES = ["api.cpp", "conv_igemm.hip", "conv3x3_halo.hip", "conv_halo8.hip", "conv_igemm8.hip", "conv1x1_stream.hip", "conv3x3_c32.hip", "conv3x3_res.hip", "conv3x3_rw.hip", "conv3x3_rw2.hip", "conv3x3_rs.hip", "c3_fused32.hip", "c3_tile.hip", "stem_body1_fused.hip", "conv_stem.hip", "conv_f32.hip", "conv_f32_pipe.hip", "preproc_pool.hip", "preproc_nv12.hip", "postprocess.hip", "classify_head.hip", "dwconv.hip", "attention.hip", "val_match.hip", "conv_i8.hip"]
+SOURCES = ["api.cpp", "conv_igemm.hip", "conv3x3_halo.hip", "conv_halo8.hip", "conv_igemm8.hip", "conv1x1_stream.hip", "conv3x3_c32.hip", "conv3x3_res.hip", "conv3x3_rw.hip", "conv3x3_rw2.hip", "conv3x3_rs.hip", "c3_fused32.hip", "c3_tile.hip", "stem_body1_fused.hip", "conv_stem.hip", "conv_f32.hip", "conv_f32_pipe.hip", "conv_f32_split.hip", "preproc_pool.hip", "preproc_nv12.hip", "postprocess.hip", "classify_head.hip", "dwconv.hip", "attention.hip", "val_match.hip", "conv_i8.hip"]
 # the conv tile x dtype space and the fused heads are instantiated in their own translation units (parallel build)
 INST_SOURCES = sorted(f for f in os.listdir(CSRC) if (f.startswith("conv_inst_") or f.startswith("head_inst_")) and f.endswith(".hip"))
 MONOLITHIC = "-DYMI_STAMPS" in os.environ.get("YOLORT_AMD_BUILD_FLAGS", "")   # the timeline instrumentation keeps one device symbol: single TU
@@ -25,7 +25,7 @@ if MONOLITHIC:
     FLAGS.append("-DYMI_MONOLITHIC")   # e.g. -DYMI_STAMPS for tools/stamp_conv.py
 # per-source flags: new translation units are compiled without the packed-fp32 instructions (v_pk_{add,mul,fma}_f32)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-SOURCE_FLAGS = {"preproc_nv12.hip": _NO_PK_F32, "classify_head.hip": _NO_PK_F32, "dwconv.hip": _NO_PK_F32, "attention.hip": _NO_PK_F32, "val_match.hip": _NO_PK_F32, "conv_i8.hip": _NO_PK_F32}
+SOURCE_FLAGS = {"preproc_nv12.hip": _NO_PK_F32, "classify_head.hip": _NO_PK_F32, "dwconv.hip": _NO_PK_F32, "attention.hip": _NO_PK_F32, "val_match.hip": _NO_PK_F32, "conv_i8.hip": _NO_PK_F32, "conv_f32_split.hip": _NO_PK_F32}
 
 
 def _hipcc() -> str:

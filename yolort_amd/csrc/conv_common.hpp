@@ -690,6 +690,8 @@ int conv_f32_launch(const ConvArgs& a, bool is1x1, hipStream_t s);
 // fp32 mode, LDS-DMA pipelined tiles 201-206 (conv_f32_pipe.hip; tile 0 = chosen from the shape by conv_f32_pick_tile)
 int conv_f32_pipe_launch(const ConvArgs& a, bool is1x1, int tile, hipStream_t s);
 int conv_f32_pick_tile(int M, int cout_pad);
+// fp32 mode on the 16-bit matrix pipe: split-bf16 tiles 211-216 (6 products) / 221-226 (8 products), the geometries of 201-206 (conv_f32_split.hip)
+int conv_f32_split_launch(const ConvArgs& a, bool is1x1, int tile, hipStream_t s);
 // 3x3 stride-1 LDS-halo kernel (conv3x3_halo.hip); returns YMI_EINVAL when the shape does not apply
 int conv3x3_halo_launch(const ConvArgs& a, int dtype, int out_dtype, int variant, hipStream_t s);
 // 8-wave LDS-halo 3x3 stride-1 kernel (conv_halo8.hip), patch shape chosen per feature-map size

@@ -188,10 +188,15 @@ int conv2d_launch(const ymi_conv_desc* d, hipStream_t s) {
     if (d->dtype == YMI_F32) {   // fp32 mode: exact fp32 arithmetic.  LDS-DMA pipelined tiles (conv_f32_pipe.hip) whenever the zero page is supplied;
         // a negative tile id (or no zero page: foreign input buffers) selects the register-staged kernel of rounds 2-4 (conv_f32.hip)
         YMI_REQUIRE(d->chain_w == nullptr, "ymi_conv2d: the fp32 mode has no chained convolution");
+        if (d->tile >= 211 && d->tile <= 226 && d->tile % 10 >= 1 && d->tile % 10 <= 6) {   // split-bf16 arithmetic on the 16-bit matrix pipe (conv_f32_split.hip): opt-in by tile id
+            YMI_REQUIRE(a.zeros != nullptr, "ymi_conv2d (fp32): the split-bf16 tiles 211-216 / 221-226 need desc.zeros (the 256-byte zero tail of x's buffer)");
+            return conv_f32_split_launch(a, is1x1, d->tile, s);
+        }
         if (d->tile >= 0 && a.zeros != nullptr) return conv_f32_pipe_launch(a, is1x1, d->tile, s);
         YMI_REQUIRE(d->y2_mode == 0, "ymi_conv2d: the register-staged fp32 kernel has no upsampled second output");
         return conv_f32_launch(a, is1x1, s);
     }
+    YMI_REQUIRE(d->tile < 211 || d->tile > 226, "ymi_conv2d: tile %d (split-bf16 arithmetic, 211-216 / 221-226) exists for fp32 descriptors only", d->tile);
     if (d->dtype == YMI_F16) {
         if (d->out_dtype == YMI_F32) return launch_dtype<YMI_F16, YMI_F32>(a, is1x1, d->tile, s);
         return launch_dtype<YMI_F16, YMI_F16>(a, is1x1, d->tile, s);

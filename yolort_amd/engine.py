@@ -233,6 +233,8 @@ def conv_out_hw(h: int, w: int, k: Tuple[int, int], s: Tuple[int, int], p: Tuple
 class Plan:
     """Owns the C plan, the activation buffers and everything the recorded pointers refer to."""
 
+    f32_split_tiles = 0   # fp32 mode: 10 / 20 with YOLORT_AMD_F32_SPLIT=6 / 8 (set in __init__), added to the shape rule's tile id
+
     def __init__(self, device: torch.device, dtype: torch.dtype):
         self.lib = _lib.load(require_gpu=True)
         if device.type != "cuda":
@@ -293,6 +295,14 @@ class Plan:
             self.res3x3 = 0
             self.rw2, self.rw3, self.rs = 0, False, False
             self.use_v1 = os.environ.get("YOLORT_AMD_F32_V1", "0") == "1"
+            # YOLORT_AMD_F32_SPLIT=6 / 8: every convolution that would take a pipelined tile 20x takes its split-bf16 form on the 16-bit matrix pipe instead (csrc/conv_f32_split.hip,
+            # tiles 21x: 6 products per k, 22x: 8; the error contract is in include/yolort_amd.h).  Opt-in: unset or 0 changes nothing.
+            split = os.environ.get("YOLORT_AMD_F32_SPLIT", "0")
+            if split not in ("0", "6", "8"):
+                raise YmiError(f"YOLORT_AMD_F32_SPLIT={split!r}: 0 (off), 6 or 8 (bf16 products per k)")
+            if split != "0" and self.use_v1:
+                raise YmiError("YOLORT_AMD_F32_SPLIT and YOLORT_AMD_F32_V1=1 exclude each other: the register-staged kernel has no split-bf16 form")
+            self.f32_split_tiles = {"0": 0, "6": 10, "8": 20}[split]   # added to the tile id the library's shape rule picks
             self.chain_1x1, self.chain_cv3 = False, False
             self.fuse_c3 = False
             self.c3_tile_on = False
@@ -445,7 +455,7 @@ class Plan:
                 d.tile = pinned if (pinned < 132 or self._pinned_ok(d, pinned)) else 0
         esz = 4 if self.fp32 else 2
         if self.fp32 and d.tile == 0 and d.zeros:
-            d.tile = int(self.lib.ymi_conv_f32_pick_tile(x.n * ho * wo, pc.cout_pad))   # what the library would choose itself: recorded so that the layer tables name the tile
+            d.tile = int(self.lib.ymi_conv_f32_pick_tile(x.n * ho * wo, pc.cout_pad)) + self.f32_split_tiles   # what the library would choose itself (+ 10 / 20: its split-bf16 form): recorded so that the layer tables and exported plans name the tile
         flops = 2.0 * x.n * ho * wo * pc.cout * pc.k_real  # algorithmic MACs (zero padding not counted)
         # algorithmic bytes follow SURVEY.md 8d: every reference conv reads its input once and writes its
         # output once; a fused cv1+cv2 launch stands for two reference convs, so its input counts twice.
